@@ -1,6 +1,22 @@
 """bench.py — CSR SpMV throughput on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c1|c2|c3|c4|c5|blur_x|blur_y|sort|cg]
+                    [--full] [--dump-outputs DIR]
+
+A plain run does what the headline figure needs and nothing more: set up,
+settle and warm up, time the K steps, write the outputs (--dump-outputs) and
+print the JSON line.  --full adds everything else the benchmark measures or
+checks, each in passes of its own after the timed steps: the CPU baselines,
+the other kernel families (alt_kernels), the device-input plan build, the
+per-step distribution (step_ms), the sampled y check (check; `sorted` for the
+sort), and the live copy / read / gather ceilings of the roofline object.
+
+--dump-outputs DIR writes what the timed path computed in its last timed
+step — the arrays its caller receives — as DIR/<name>.npy (float32 or
+float64; rank 0).  Arrays that would pass 64 MB together are written as a
+fixed, seeded sample of their elements (dump_outputs: the same positions in
+every run).  Every input is seeded, so two runs with the same arguments dump
+the outputs of the same problem.
 
 N=1: BASELINE configs[1] — CSR SpMV, n=10M, nnz=150M (exactly 15 uniform
 distinct sorted columns per row), fp32 values/x/y, A and x resident in HBM.
@@ -28,8 +44,8 @@ Extra objects on the JSON line:
                 events on the launch stream; peak 8.0 TB/s; traffic = PMC
                 fabric bytes per call from profiles/traffic.json (or null);
                 layout = the same call against the bytes the XTILE layout
-                streams.
-  cpu_baseline  rank 0, N=1 only: the AVX2 + OpenMP CSR SpMV of oracle/ (the
+                streams.  --full adds the live ceilings (copy, gather).
+  cpu_baseline  --full, rank 0, N=1 only: the AVX2 + OpenMP CSR SpMV of oracle/ (the
                 reference has no CPU SpMV) on the same matrix, timed
                 for ~10 s on the box's host cores (OpenMP placement and host
                 CPU / NUMA nodes recorded in the object).
@@ -131,7 +147,55 @@ def parse():
     ap.add_argument("--dtype", default="auto", choices=["auto", "f32", "f64"],
                     help="SpMV value type (auto: the config's own — fp64 for c1/c3, fp32 for c2/c4; "
                          "SURVEY §8d also runs C4 in fp64)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure, in passes of their own after the timed steps: CPU "
+                         "baselines, alt_kernels, the device-input plan build, step_ms, the y check, the live "
+                         "copy / read / gather ceilings (off: set up, warm up, time the steps, print the line)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the arrays the last timed step computed as DIR/<name>.npy (float32 / float64, "
+                         "at most 64 MB in all: a fixed seeded sample of larger ones); rank 0")
+    args = ap.parse_args()
+    if not args.full:  # the baselines and the other kernel families belong to --full
+        args.no_cpu_baseline = args.no_alt_kernels = True
+    return args
+
+
+DUMP_BUDGET = 60 * 1000 * 1000  # --dump-outputs: array bytes in all (64 MB with room for the .npy headers)
+DUMP_SEED = 0x5EED00D0
+
+
+def dump_outputs(path, arrays, unsigned=()):
+    """--dump-outputs: `arrays` (name -> device tensor or numpy array) as
+    path/<name>.npy, float64 for 8-byte and integer element types (uint32
+    keys are exact in it; `unsigned` names signed integer arrays that hold
+    unsigned values), else float32.  When the whole set would pass
+    DUMP_BUDGET every array is cut to its share of it: m elements at sorted
+    positions drawn uniformly by a generator seeded with DUMP_SEED, so the
+    positions depend only on the array's length and m.  The gather runs on
+    the device for tensors (the whole array never crosses to the host)."""
+    os.makedirs(path, exist_ok=True)
+    out_dt, total = {}, 0
+    for name, a in arrays.items():
+        is_np = isinstance(a, np.ndarray)
+        dt = a.dtype if is_np else np.dtype(str(a.dtype).replace("torch.", ""))
+        out_dt[name] = np.float32 if (dt.kind == "f" and dt.itemsize <= 4) else np.float64
+        total += int(a.size if is_np else a.numel()) * np.dtype(out_dt[name]).itemsize
+    for name, a in arrays.items():
+        is_np = isinstance(a, np.ndarray)
+        flat = a.reshape(-1)
+        count = int(flat.size if is_np else flat.numel())
+        if total > DUMP_BUDGET:
+            m = min(count, DUMP_BUDGET // len(arrays) // np.dtype(out_dt[name]).itemsize)
+            idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, count, size=m))
+            if is_np:
+                flat = flat[idx]
+            else:
+                import torch
+                flat = flat[torch.from_numpy(idx).to(flat.device)]
+        host = flat if is_np else flat.cpu().numpy()
+        if name in unsigned:
+            host = host.view(np.dtype(f"u{host.dtype.itemsize}"))
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(host).astype(out_dt[name]))
 
 
 def cpu_threads():
@@ -312,6 +376,9 @@ def main():
 
             def step():
                 plans[0](xd, y_local, stream=stream)
+
+            def step_output():  # --dump-outputs: y of the last step
+                return y_local
         elif native_dist:
             # native path behind the C ABI (lhpc_dist_spmv): nnz-balanced
             # interleaved blocks, K chunks per rank; chunk k is reduced into
@@ -537,9 +604,15 @@ def main():
 
                 def step_end():
                     dplan.end(stream=stream)
+
+                def step_output():  # the buffer the last begin wrote
+                    return ch_bufs[ch_cur[0]]
             else:
                 def step():
                     dplan(xd, y_out_buf, stream=stream)
+
+                def step_output():
+                    return y_out_buf
         else:
             # torch.distributed form (gloo rehearsal, LHPC_DIST_TORCH=1):
             # interleaved nnz-balanced row blocks, K chunks per rank; chunk
@@ -573,13 +646,17 @@ def main():
                 fns = [lambda xv, yv, pl=pl: pl(xv, yv, stream=stream) for pl in plans]
             local_rows = ib.B * n_chunks
             dsp = DistSpMVOverlap(ib, fns, like=xd)
+            y_last = [None]
 
             def step():
-                dsp.step(xd)
+                y_last[0] = dsp.step(xd)
+
+            def step_output():
+                return y_last[0]
         t_plan = time.time() - t0
         info = plans[0].info()
         t_plan_dev = None
-        if world == 1 and not native_dist and info["kernel"] == L.KERNEL_XTILE and wl in ("c2", "c3", "c4"):
+        if args.full and world == 1 and not native_dist and info["kernel"] == L.KERNEL_XTILE and wl in ("c2", "c3", "c4"):
             # the same plan from device-resident CSR (LHPC_PLAN_DEVICE_INPUT:
             # the XTILE layout built on the GPU), timed beside the host build
             drp, dcol, dval = (torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (rp, col, val))
@@ -613,18 +690,22 @@ def main():
         ev1.record(stream)
         barrier()
         t_wall = time.perf_counter() - t_wall0
-        # the per-step distribution (median of per-rep timings) in a
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, {"y": step_output()})
+        # --full: the per-step distribution (median of per-rep timings) in a
         # second pass with an event at every step boundary, outside the timed
         # region: a timing event between two calls leaves the GPU idle ≈ 6 µs
         # (rocprof trace, round 5), which the headline run must not carry
-        sev = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
-        for i in range(args.steps):
-            sev[i].record(stream)
-            step()
-        step_end()
-        sev[args.steps].record(stream)
-        barrier()
-        step_ms = np.array([sev[i].elapsed_time(sev[i + 1]) for i in range(args.steps)])
+        step_ms = None
+        if args.full:
+            sev = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
+            for i in range(args.steps):
+                sev[i].record(stream)
+                step()
+            step_end()
+            sev[args.steps].record(stream)
+            barrier()
+            step_ms = np.array([sev[i].elapsed_time(sev[i + 1]) for i in range(args.steps)])
         t_ev = ev0.elapsed_time(ev1) * 1e-3
         elapsed = max(t_wall, t_ev)
         timing = {"wall_s": t_wall, "events_s": t_ev, "value_from": "wall" if t_wall >= t_ev else "events"}
@@ -635,23 +716,27 @@ def main():
         per_step = elapsed / args.steps
         gflops = 2.0 * nnz / per_step / 1e9
         alg_bytes = nnz * (tsz + 4) + (n + 1) * 4 + 2 * n * tsz
-        # live SpMV-call timing on rank 0's launch stream (kernel-only, no collective)
-        kev0 = torch.cuda.Event(enable_timing=True)
-        kev1 = torch.cuda.Event(enable_timing=True)
-        reps = max(args.steps, 10)
-        barrier()
-        ysc = torch.empty(max(pl.n_rows for pl in plans), dtype=xd.dtype, device=dev)
-        kev0.record(stream)
-        for _ in range(reps):
-            for pl in plans:
-                pl(xd, ysc[:pl.n_rows], stream=stream)
-        kev1.record(stream)
-        torch.cuda.synchronize()
-        call_loop_s = kev0.elapsed_time(kev1) * 1e-3 / reps
+        # live SpMV-call timing on rank 0's launch stream (kernel-only, no collective):
+        # a pass of its own, so at N = 1 only with --full
+        single = world == 1 and not native_dist
+        call_loop_s = None
+        if args.full or not single:
+            kev0 = torch.cuda.Event(enable_timing=True)
+            kev1 = torch.cuda.Event(enable_timing=True)
+            reps = max(args.steps, 10)
+            barrier()
+            ysc = torch.empty(max(pl.n_rows for pl in plans), dtype=xd.dtype, device=dev)
+            kev0.record(stream)
+            for _ in range(reps):
+                for pl in plans:
+                    pl(xd, ysc[:pl.n_rows], stream=stream)
+            kev1.record(stream)
+            torch.cuda.synchronize()
+            call_loop_s = kev0.elapsed_time(kev1) * 1e-3 / reps
         # N = 1: the call time is the timed region's own (HIP events on the
         # launch stream around exactly the K timed steps); N > 1 steps hold the
         # exchange too, so there the kernel-only loop above gives the call
-        call_s = t_ev / args.steps if (world == 1 and not native_dist) else call_loop_s
+        call_s = t_ev / args.steps if single else call_loop_s
         local_alg = local_nnz * (tsz + 4) + (local_rows + len(plans)) * 4 + (n + local_rows) * tsz
         achieved = local_alg / call_s / 1e9
         kname = {L.KERNEL_XSLICE: "xslice", L.KERNEL_ROWGROUP: "rowgroup", L.KERNEL_ADAPTIVE: "adaptive",
@@ -687,24 +772,27 @@ def main():
             roofline={"bound": "hbm", "kernel": kernels, "achieved": achieved, "peak": HBM_PEAK_GBPS,
                       "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic,
                       "alg_bytes_per_call": local_alg, "call_us": call_s * 1e6,
-                      "call_us_source": "HIP events over the timed region" if (world == 1 and not native_dist)
-                      else "kernel-only loop of the rank's local calls", "call_us_kernel_loop": call_loop_s * 1e6},
+                      "call_us_source": "HIP events over the timed region" if single
+                      else "kernel-only loop of the rank's local calls",
+                      **({"call_us_kernel_loop": call_loop_s * 1e6} if call_loop_s is not None else {})},
             timing=timing, settle=settled,
-            step_ms={"median": float(np.median(step_ms)), "p10": float(np.percentile(step_ms, 10)),
-                     "p90": float(np.percentile(step_ms, 90)),
-                     "source": "rank 0 HIP events per step, in a second untimed pass of the same K steps"},
             setup_s={"generate": t_gen, "plan": t_plan,
                      **({"plan_device_input": t_plan_dev, "device_layout_identical": same} if t_plan_dev else {})},
         )
-        # correctness of the timed output, outside the timed region: y of the
-        # last step on 10^5 sampled rows against an fp64 numpy evaluation,
-        # |dy| <= 1e-6·Σ|a·x| per row (the parity bar of tests/_support.py)
+        if step_ms is not None:
+            result["step_ms"] = {"median": float(np.median(step_ms)), "p10": float(np.percentile(step_ms, 10)),
+                                 "p90": float(np.percentile(step_ms, 90)),
+                                 "source": "rank 0 HIP events per step, in a second untimed pass of the same K steps"}
         if native_dist:
             result["exchange"] = exchange_report
-        y_out = dsp.step(xd) if (world > 1 or native_dist) else y_local  # every rank: the step holds collectives
-        if rank == 0:
-            result["check"] = sampled_y_check(rp, col, val, x, y_out.cpu().numpy(), 100_000)
-        if kname == "xslice" and rank == 0:
+        # --full: correctness of the timed output, outside the timed region: y of
+        # one more step on 10^5 sampled rows against an fp64 numpy evaluation,
+        # |dy| <= 1e-6·Σ|a·x| per row (the parity bar of tests/_support.py)
+        if args.full:
+            y_out = dsp.step(xd) if (world > 1 or native_dist) else y_local  # every rank: the step holds collectives
+            if rank == 0:
+                result["check"] = sampled_y_check(rp, col, val, x, y_out.cpu().numpy(), 100_000)
+        if args.full and kname == "xslice" and rank == 0:
             result["roofline"]["gather"] = gather_ceiling(L, torch, dev, stream, local_nnz, call_s)
         if kname == "xtile":
             # bytes the XTILE layout streams per call: gather reads
@@ -714,7 +802,7 @@ def main():
             result["roofline"]["layout"] = {"stream_bytes_per_call": stream_b,
                                             "achieved": stream_b / call_s / 1e9,
                                             "frac": stream_b / call_s / 1e9 / HBM_PEAK_GBPS}
-        if rank == 0 and world == 1:
+        if args.full and rank == 0 and world == 1:
             # the attainable rate for the bytes this call streams (the layout's
             # for XTILE, else the algorithmic ones), measured live
             lay = result["roofline"].get("layout")
@@ -964,6 +1052,8 @@ def stencil_bench(args, L, torch, dev, stream, barrier):
     wl = args.workload
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
+    gen = torch.Generator(device=dev)  # seeded inputs: the same grid in every run
+    gen.manual_seed(0x5EED0005 + rank)
     if wl == "c5":
         n = 512
         g = 1
@@ -973,7 +1063,7 @@ def stencil_bench(args, L, torch, dev, stream, barrier):
         force_native = os.environ.get("LHPC_DIST_NATIVE", "0") == "1" and "RANK" in os.environ
         if world == 1 and not force_native:
             u = torch.zeros(P ** 3, device=dev)
-            u.view(P, P, P)[1:-1, 1:-1, 1:-1] = torch.rand(n, n, n, device=dev) * 2 - 1
+            u.view(P, P, P)[1:-1, 1:-1, 1:-1] = torch.rand(n, n, n, device=dev, generator=gen) * 2 - 1
             o = torch.zeros_like(u)
             fn = lambda: L.stencil7(u, o, n, n, n, g, -6.0, 1.0, stream=stream)  # noqa: E731
             workload = "BASELINE configs[4] grid: 7-point 3-D stencil 512^3 fp32, 1 GPU"
@@ -982,7 +1072,7 @@ def stencil_bench(args, L, torch, dev, stream, barrier):
             z0, z1 = slab_bounds(n, rank, world)
             nzl = z1 - z0
             u = torch.zeros((nzl + 2) * P * P, device=dev)
-            u.view(nzl + 2, P, P)[1:-1, 1:-1, 1:-1] = torch.rand(nzl, n, n, device=dev) * 2 - 1
+            u.view(nzl + 2, P, P)[1:-1, 1:-1, 1:-1] = torch.rand(nzl, n, n, device=dev, generator=gen) * 2 - 1
             o = torch.zeros_like(u)
             import torch.distributed as dist
             has_rccl = dist.get_backend() == "nccl" and os.environ.get("LHPC_DIST_TORCH", "0") != "1"
@@ -1029,7 +1119,7 @@ def stencil_bench(args, L, torch, dev, stream, barrier):
             workload = f"BASELINE configs[4]: 7-point 3-D stencil 512^3 fp32, z-slabs x{world} + {how}"
     else:
         n, g = 8192, 8
-        a = torch.rand((n + 2 * g) ** 2, device=dev) * 2 - 1
+        a = torch.rand((n + 2 * g) ** 2, device=dev, generator=gen) * 2 - 1
         b = torch.empty(n * n, device=dev)
         f = L.blur_x if wl == "blur_x" else L.blur_y
         fn = lambda: f(a, b, n, n, g, 8, stream=stream)  # noqa: E731
@@ -1053,8 +1143,10 @@ def stencil_bench(args, L, torch, dev, stream, barrier):
         tt = torch.tensor([per], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         per = float(tt.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"out": o if wl == "c5" else b})
     ach = 8.0 * cells / per / 1e9 / world
-    copy = copy_ceiling(L, torch, dev, stream, int(8 * cells // world), ach) if rank == 0 else None
+    copy = copy_ceiling(L, torch, dev, stream, int(8 * cells // world), ach) if (args.full and rank == 0) else None
     out = dict(metric=f"{wl} Gcell/s (8 B/cell algorithmic)", value=cells / per / 1e9, unit="Gcell/s",
                n_gpus=world, steps=args.steps, warmup=args.warmup, ms_per_step=per * 1e3,
                higher_is_better=True, scaling="strong" if wl == "c5" else "weak", vs_baseline=None, dtype="f32",
@@ -1151,9 +1243,12 @@ def cg_bench(args, L, torch, dev, stream, barrier, world, rank):
     run(max(10, args.warmup))
     barrier()
     t0 = time.perf_counter()
-    _, it, res = run(args.steps)
+    x_out, it, res = run(args.steps)
     barrier()
     per = (time.perf_counter() - t0) / args.steps
+    if args.dump_outputs and rank == 0:
+        # the iterate after `steps` iterations (the rank's rows under torch.distributed's DistCG)
+        dump_outputs(args.dump_outputs, {"x": x_out})
     if world > 1:
         import torch.distributed as dist
         tt = torch.tensor([per], dtype=torch.float64, device=dev)
@@ -1243,7 +1338,11 @@ def sort_bench(args, L, torch, dev, stream, barrier, world, rank):
         tt = torch.tensor([per], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         per = float(tt.item())
-    ok = bool((keys[1:].to(torch.int64) & 0xFFFFFFFF).ge(keys[:-1].to(torch.int64) & 0xFFFFFFFF).all())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"keys": keys}, unsigned=("keys",))  # uint32 keys in an int32 tensor
+    # --full: the whole output checked for order (a pass over 500M keys)
+    ok = bool((keys[1:].to(torch.int64) & 0xFFFFFFFF).ge(keys[:-1].to(torch.int64) & 0xFFFFFFFF).all()) \
+        if args.full else None
     value = world * n / per / 1e9
     alg = 32.0 * n  # 4 passes x (read + write) x 4 B per key
     out = dict(metric="radix sort G keys/s, 500M uint32 keys (reference README.md:52)", value=value,

@@ -65,6 +65,46 @@ def test_spmv_options_forms():
     assert bench.parse_options("xtile_steps=4,xtile_piece=150000") == {"xtile_steps": 4, "xtile_piece": 150000}
 
 
+def test_full_is_off_by_default_and_gates_the_side_measurements(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    a = bench.parse()
+    assert not a.full and a.dump_outputs is None and a.steps == 3 and a.warmup == 1
+    assert a.no_cpu_baseline and a.no_alt_kernels  # a plain run measures neither
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "d" and not a.no_cpu_baseline and not a.no_alt_kernels
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-cpu-baseline"])
+    a = bench.parse()
+    assert a.no_cpu_baseline and not a.no_alt_kernels
+
+
+def test_dump_outputs_small_arrays_whole(tmp_path):
+    import numpy as np
+    y32 = np.arange(1000, dtype=np.float32) / 7
+    y64 = np.arange(77, dtype=np.float64) / 3
+    keys = np.array([0, 1, -1, -2**31], dtype=np.int32)  # uint32 keys in int32 storage
+    bench.dump_outputs(str(tmp_path / "d"), {"y32": y32, "y64": y64, "keys": keys}, unsigned=("keys",))
+    a, b, k = (np.load(tmp_path / "d" / f"{n}.npy") for n in ("y32", "y64", "keys"))
+    assert a.dtype == np.float32 and np.array_equal(a, y32)
+    assert b.dtype == np.float64 and np.array_equal(b, y64)
+    assert k.dtype == np.float64 and k.tolist() == [0.0, 1.0, 2.0**32 - 1, 2.0**31]
+
+
+def test_dump_outputs_samples_past_the_budget(tmp_path, monkeypatch):
+    import numpy as np
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 4000)
+    y = np.arange(5000, dtype=np.float32)  # 20 kB > the budget: half of it, 500 sampled elements
+    z = np.arange(300, dtype=np.float64)   # the other half: 250 elements
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"y": y, "z": z})
+    ya, yb = np.load(tmp_path / "a" / "y.npy"), np.load(tmp_path / "b" / "y.npy")
+    za = np.load(tmp_path / "a" / "z.npy")
+    assert ya.dtype == np.float32 and ya.size == 500 and za.size == 250
+    assert ya.nbytes + za.nbytes <= 4000
+    assert np.array_equal(ya, yb)  # the same positions in every run
+    assert np.all(np.diff(ya) >= 0) and np.all(np.isin(ya, y)) and np.unique(ya).size > 400
+
+
 def test_exchange_model_arithmetic():
     """bench.py's `exchange.model` (tools/step_model.exchange_model): the
     measured receive / per-link rate from the exchange-only time, and the
