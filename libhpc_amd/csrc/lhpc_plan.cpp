@@ -156,6 +156,167 @@ int build_xslice(const void *rp, int bits, const int32_t *col, const void *val, 
   return LHPC_OK;
 }
 
+// XTILE column blocks (lhpc_options.xtile_col_blocks).  A reduce chunk holds
+// M nonzeros and meets every one of the S tiles, so its segment per tile is
+// M/S nonzeros: 32 for C2 (S = 256), 4 at n = 80M (S = 2048), and the
+// reduce's cost per nonzero grows with S (DESIGN.md §4 "large n": 632 GFLOP/s
+// at S = 256, 533 at 768, 408 at 1024, 244 at 2048).  Cutting the columns into
+// B blocks gives each block's plan S/B tiles; the blocks run in turn on x's
+// column ranges, every block after the first adding into y.  A chunk also
+// holds ≤ M/8 rows, so as a block's rows get shorter its chunks shrink with
+// the blocks.  Same box, fp32 15 per row, forced B (profiles/r04/col_blocks):
+// n = 10M (256 tiles) B = 1 / 2: 601 / 534 GFLOP/s; 40M (1024) B = 2 / 3 /
+// 4: 498 / 446 / 426; 80M (2048) B = 2 / 3 / 4 / 6: 378 / 417 / 365 / 314;
+// 150M (3840, two row parts) B = 2 / 3 / 4: 316 / 371 / 342.  fp64 10M (489)
+// B = 1 / 2: 318 / 304; 40M (1954) B = 2 / 3 / 4 / 6: 264 / 261 / 230 / 180.
+// Hence B = ⌈S / 768⌉, at most mean row length / 5.
+constexpr int64_t kColBlockTiles = 768;
+static int xtile_col_blocks_for(int64_t n_rows, int64_t n_cols, int64_t nnz, int64_t S, const lhpc_options &o) {
+  const int64_t most = std::max<int64_t>(1, n_cols / 64);  // ≥ 64 columns per block
+  if (o.xtile_col_blocks > 0) return static_cast<int>(std::min<int64_t>(o.xtile_col_blocks, most));
+  if (S <= kColBlockTiles || n_rows <= 0) return 1;
+  const double mean = static_cast<double>(nnz) / static_cast<double>(n_rows);
+  const int64_t bmax = std::max<int64_t>(1, static_cast<int64_t>(mean / 5.0));
+  return static_cast<int>(std::min({(S + kColBlockTiles - 1) / kColBlockTiles, bmax, most}));
+}
+
+XtilePartition xtile_partition_policy(int64_t n_rows, int64_t n_cols, int64_t nnz, size_t elem_bytes, int n_splits,
+                                      const lhpc_options &o) {
+  XtilePartition r;
+  const int64_t W = xtile_capacity(elem_bytes);
+  r.tiles = (n_cols + W - 1) / W;
+  // row parts when the tile stream outgrows its int32 offsets (or a lower
+  // cap is asked for); user row splits keep a single plan
+  // and column blocks when x spans many tiles (xtile_col_blocks_for)
+  r.cap = INT32_MAX - 8 * (r.tiles + 256) - (int64_t{1} << 16);
+  if (o.xtile_part_nnz > 0) r.cap = std::min<int64_t>(r.cap, o.xtile_part_nnz);
+  r.col_blocks = n_splits == 0 ? xtile_col_blocks_for(n_rows, n_cols, nnz, r.tiles, o) : 1;
+  r.parts = (nnz > r.cap || r.col_blocks > 1) && n_splits == 0 &&
+            (r.tiles + r.col_blocks - 1) / r.col_blocks <= kXtMaxTiles;
+  return r;
+}
+
+int64_t xtile_tile_width(int64_t n_cols, size_t elem_bytes, int cus, int narrow_override) {
+  // tile width: the LDS capacity XtTile<T>::W, narrowed for fp32 so that the
+  // tile count is a whole multiple of the CUs when that adds ≤ 10% tiles
+  // (C2: 245 → 256 tiles of 39063 columns): a cache-sized range's gather
+  // round of one piece per tile then fills every CU.  fp64 (single range,
+  // ≈ 2 pieces per CU) lost 3% with it (C3 489 → 512 tiles: 0.913 → 0.941 ms)
+  const int64_t W = xtile_capacity(elem_bytes);
+  const int64_t s0 = (n_cols + W - 1) / W, s1 = (s0 + cus - 1) / cus * cus;
+  // (never past build_xtile's 4096-tile cap: on a CU count that does not
+  // divide 4096 the rounding could otherwise cost a plan its XTILE layout)
+  bool narrow = elem_bytes == 4 && s1 * 10 <= s0 * 11 && s1 <= kXtMaxTiles;
+  if (narrow_override >= 0) narrow = narrow_override != 0;
+  return narrow && s1 > s0 ? (n_cols + s1 - 1) / s1 : W;
+}
+
+XtilePolicy xtile_policy(const XtileShape &s, const lhpc_options &o) {
+  XtilePolicy r;
+  const int64_t tsz = s.elem_bytes, W = s.W, cus = s.cus;
+  const int M = s.M;
+  const bool user_splits = s.n_user_splits > 0;
+  r.W = W;
+  r.tiles = (s.n_cols + W - 1) / W;
+  r.nnz = s.nnz;
+  r.cus = s.cus;
+  // ≈ 2 gather workgroups per CU (one resident per CU: 160 KB of LDS each)
+  // and ≥ 4 tiles' worth of stream per piece, so the tile load (W·T bytes)
+  // stays ≤ 1/4 of a piece's col16 + xg traffic on small (per-rank) matrices
+  r.min_piece = 4 * W * tsz / (2 + tsz);
+  r.piece = std::max<int64_t>(r.min_piece, s.nnz / (2 * cus) + 1);
+  if (o.xtile_piece > 0) r.piece = std::max<int64_t>(8, o.xtile_piece);
+  // reduce index stream: iperm (gather each CSR position's x from the flat
+  // segment concatenation in LDS), else perm (scatter into CSR slots).  Round
+  // 1 kept perm below 32 full chunks per CU (per-rank matrices at N ≥ 4);
+  // with the reduce as it is now iperm is as fast or faster there too — same
+  // box, local work of rank 0 (tools/explore_rank_reduce.py,
+  // profiles/r04/rank_reduce.jsonl): fp32 W = 4 0.132 → 0.118 ms, W = 8
+  // 0.0656 → 0.0653; fp64 W = 4 0.263 → 0.245, W = 8 0.125 → 0.118
+  bool ip = true;
+  if (o.xtile_reduce != LHPC_XTILE_REDUCE_AUTO) ip = o.xtile_reduce == LHPC_XTILE_REDUCE_IPERM;
+  // the iperm reduce addresses xg with 32-bit buffer offsets: stream + tile
+  // padding (≤ 8 per tile) + one piece of slack must stay below 2 GiB
+  const int64_t stream_max = s.nnz + 8 * r.tiles + 2 * M;
+  if (stream_max * tsz >= (int64_t{1} << 31)) ip = false;
+  r.iperm = ip;
+  // aligned segments (iperm only): each (tile, chunk) segment padded to 16 B
+  // (≤ VW − 1 entries per segment, ≤ 3 per 4 nonzeros in the worst case)
+  const int64_t VW = 16 / tsz;
+  bool al = false;
+  if (o.xtile_align == LHPC_XTILE_ALIGN_UNITS) al = true;
+  if (al && (!ip || (stream_max + (VW - 1) * std::min<int64_t>(s.nnz, r.tiles * (s.nnz / (M / 2) + 2))) * tsz >=
+                        (int64_t{1} << 31)))
+    al = false;
+  // the fp32 aligned reduce with 8 segment-table entries per thread (S > 2048
+  // tiles, n_cols > 84M) would spill a VGPR: packed segments there
+  if (al && s.G > 4) al = false;
+  r.aligned = al;
+  r.supported = !(s.dev_build && al);  // aligned segments: host build only
+  // chunk cuts: at the last row start in the back M/32 of the window, else
+  // mid-row (the row's pieces meet in k_xtile_fixup).  Per-chunk costs are
+  // fixed, so full chunks matter on skewed rows: C4 has 19803 chunks when any
+  // row start in the back half is taken, 18454 with the back M/32 (C2: 18316
+  // either way); options.xtile_cut overrides (entries, 1..M)
+  r.cut = M / 32;
+  if (o.xtile_cut > 0) r.cut = std::min(M, o.xtile_cut);
+  // the xg ring (options.xtile_ring): the plan's own cache
+  // ranges by default; user row ranges only when asked for (xtile_ring = 2:
+  // the library's per-rank plans, which gather and reduce range by range in
+  // order — lhpc_spmv_stage would gather every range into the one ring: a
+  // ring plan refuses it)
+  r.ring_ok = ip && !al && (user_splits ? o.xtile_ring == 2 : o.xtile_ring != 1);
+  // cache-sized ranges: K nnz-balanced row ranges, gathered and reduced in
+  // turn, so that each range's xg (≈ 200 MB) is still in the 256 MB Infinity
+  // Cache when its reduce reads it back.  fp32 only: each extra range re-reads
+  // x (n_cols·T) in its gather.  Same box: C2 reduce 352 → 295
+  // µs, gather 163 → 179 µs, call 523.5 → 483.8 µs at K = 3 (K = 4: 506.7);
+  // C3 (fp64, K = 6: 200 MB ranges) 928 → 944 µs, so not for fp64 — until
+  // the xg ring (round 6, same box, xtile_ranges = 1 / 3 / 4 / 6 / 8: C3
+  // 0.908 / 0.943 / 0.995 / 0.868 / 0.902 ms): fp64 takes the ranges when its
+  // plan can hold the ring (no user row splits, iperm reduce).
+  // Only while each range still streams ≥ min_piece nonzeros per tile (fp64:
+  // min_piece / 2 — its ring saves the 8-B xg write-back) and K ≤ 8: every
+  // range re-loads all S tiles of x, so a wide x (n = 80M: 1954 tiles; n =
+  // 150M: 3662) would spend more on tile loads than the cache saves — such
+  // plans keep one range (the n = 150M plan took 23.6 ms with 8 ranges per part)
+  const int64_t xg_bytes = s.nnz * tsz;
+  r.past_cache = xg_bytes > (int64_t{256} << 20);
+  {
+    const int64_t k = (xg_bytes + (int64_t{200} << 20) - 1) / (int64_t{200} << 20);
+    const int64_t need = tsz == 4 ? r.min_piece : r.min_piece / 2;
+    if ((tsz == 4 || r.ring_ok) && r.past_cache && k <= 8 && s.nnz / k / std::max<int64_t>(1, r.tiles) >= need)
+      r.ranges = static_cast<int>(k);
+  }
+  if (o.xtile_ranges > 0) r.ranges = o.xtile_ranges;
+  // without user splits the ranges are the plan's own nnz-balanced row cuts
+  r.own_cuts = !user_splits && r.ranges > 1 && s.n_rows >= 2LL * r.ranges;
+  // phase-A tables (options.xtile_pretable): iperm
+  // plans without aligned segments, G = 1.  Default for fp64 only — same box,
+  // two runs each: C3 reduce 89.9 → 85.3 µs per range (its 16-wave scan was
+  // 2.3K of 27.8K cycles per chunk), C2 88.1 → 89.4 µs (the tables' extra
+  // 2 KB per chunk outweigh an 8-wave scan)
+  r.pre = ip && !al && s.G == 1 && (o.xtile_pretable == 2 || (o.xtile_pretable == 0 && tsz == 8));
+  if (o.xtile_steps > 0) {
+    const int u = o.xtile_steps;
+    r.steps = u <= 2 ? 2 : u < 8 ? 4 : u < 16 ? 8 : 16;
+  }
+  // non-temporal xg stores when the xg of a single-range plan exceeds the 256
+  // MB Infinity Cache anyway (same box, two runs each: C3 918.6 → 908.8 µs
+  // median); cache-sized ranges need their xg to stay there (C2 with them
+  // non-temporal: 473 → 536 µs)
+  r.store = o.xtile_store;
+  r.range_piece_opt = o.xtile_range_piece;
+  return r;
+}
+
+int64_t XtilePolicy::range_piece(int K) const {
+  // one gather round per range: ≈ one piece per (tile, range) part, so each
+  // range loads every tile once (only one 160-KB gather block fits a CU)
+  if (range_piece_opt > 0) return std::max<int64_t>(8, range_piece_opt);
+  return std::max<int64_t>(min_piece, nnz / K / static_cast<int64_t>(cus) * 5 / 4 + 1);
+}
+
 int xtile_plan_chunks(const void *rp, int bits, const int32_t *col, int64_t n_rows, int64_t n_cols, int64_t W,
                       int M, int Rmax, int slot_bytes, const int64_t *splits, int n_splits, bool iperm,
                       int cut_window, XtileHost &o, int unit) {
@@ -164,7 +325,7 @@ int xtile_plan_chunks(const void *rp, int bits, const int32_t *col, int64_t n_ro
       cut_window < 1 || cut_window > M || (unit != 1 && unit != 2 && unit != 4) || (unit > 1 && !iperm))
     return LHPC_ERR_INVALID_ARG;
   const int64_t S = n_cols > 0 ? (n_cols + W - 1) / W : 1;
-  if (S > 4096 || nnz + 8 * S >= INT32_MAX || n_rows >= INT32_MAX) return LHPC_ERR_UNSUPPORTED;
+  if (S > kXtMaxTiles || nnz + 8 * S >= INT32_MAX || n_rows >= INT32_MAX) return LHPC_ERR_UNSUPPORTED;
   o.S = static_cast<int>(S);
   o.W = W;
   o.M = M;
@@ -394,14 +555,21 @@ int build_xtile(const void *rp, int bits, const int32_t *col, int64_t n_rows, in
   return LHPC_OK;
 }
 
-int xtile_transpose_runs(const XtileHost &o, const void *val, size_t tsz, int run, int64_t tail,
-                         std::vector<int32_t> &vbase, std::unique_ptr<unsigned char[]> &valt,
-                         std::unique_ptr<uint16_t[]> &ipt) {
+int xtile_run_bases(const XtileHost &o, int run, int64_t tail, std::vector<int32_t> &vbase) {
   const int64_t C = o.n_chunks, reg = 64 * static_cast<int64_t>(run);
   std::vector<int64_t> vb(static_cast<size_t>(C) + 1, 0);
   for (int64_t c = 0; c < C; ++c) vb[c + 1] = vb[c] + (o.ce[c + 1] - o.ce[c] + reg - 1) / reg * reg;
   if (vb[C] + tail >= INT32_MAX) return LHPC_ERR_UNSUPPORTED;
   vbase.assign(vb.begin(), vb.end());
+  return LHPC_OK;
+}
+
+int xtile_transpose_runs(const XtileHost &o, const void *val, size_t tsz, int run, int64_t tail,
+                         std::vector<int32_t> &vbase, std::unique_ptr<unsigned char[]> &valt,
+                         std::unique_ptr<uint16_t[]> &ipt) {
+  const int64_t C = o.n_chunks;
+  if (const int st = xtile_run_bases(o, run, tail, vbase)) return st;
+  const std::vector<int32_t> &vb = vbase;
   const size_t total = static_cast<size_t>(vb[C] + tail);
   valt.reset(new unsigned char[total * tsz]());
   if (o.iperm) {  // padding points at the reduce's zero slot M (x = 0 there)

@@ -7,6 +7,8 @@
 #include <memory>
 #include <vector>
 
+#include "../../include/lhpc.h"
+
 namespace lhpc {
 
 // CSR sanity, always run by lhpc_spmv_plan_create before any layout pass
@@ -132,9 +134,69 @@ int build_xtile(const void *row_ptr, int rp_bits, const int32_t *col, int64_t n_
                 const int64_t *splits, int n_splits, bool iperm, int cut_window, XtileHost &out,
                 int unit = 1);
 
+// The decisions of an XTILE plan build, as pure functions of the shape and
+// the options (no HIP call, no environment), so that a host test can put the
+// full-size shapes to them (tests/cpp/asan_plan.cpp).  lhpc_spmv.hip asks
+// xtile_partition_policy, build_t of lhpc_spmv_xtile.hip the other two.
+//
+// One tile of x fills a gather workgroup's LDS: 160 KB of T
+constexpr int64_t xtile_capacity(size_t elem_bytes) { return 160 * 1024 / static_cast<int64_t>(elem_bytes); }
+constexpr int kXtMaxTiles = 4096;  // tiles of one plan (build_xtile)
+
+// How a matrix becomes XTILE plans: tiles of x at full capacity, cap = the
+// nonzeros one plan's int32 stream offsets hold (or options.xtile_part_nnz),
+// col_blocks column blocks, and parts: whether the matrix is cut into row
+// parts × column blocks (build_parts) instead of one plan.  User row splits
+// (n_splits > 0) keep a single plan.
+struct XtilePartition {
+  int64_t tiles = 0, cap = 0;
+  int col_blocks = 1;
+  bool parts = false;
+};
+XtilePartition xtile_partition_policy(int64_t n_rows, int64_t n_cols, int64_t nnz, size_t elem_bytes, int n_splits,
+                                      const lhpc_options &o);
+
+// tile width: the capacity, narrowed for fp32 to a whole multiple of the CUs
+// when that adds ≤ 10% tiles; narrow: −1 by that rule, 0 / 1 override it
+int64_t xtile_tile_width(int64_t n_cols, size_t elem_bytes, int cus, int narrow = -1);
+
+// M: nonzeros per reduce chunk; W: xtile_tile_width; G: segment-table entries
+// per reduce thread at ⌈n_cols / W⌉ tiles (at most kXtMaxTiles; the kernel
+// file's xtile_g, which knows the reduce's LDS carve-up); dev_build: the
+// O(nnz) passes run on the GPU
+struct XtileShape {
+  int64_t n_rows = 0, n_cols = 0, nnz = 0;
+  int elem_bytes = 4, M = 0, cus = 256, n_user_splits = 0;
+  bool dev_build = false;
+  int64_t W = 0;
+  int G = 1;
+};
+struct XtilePolicy {
+  int64_t W = 0, tiles = 0;
+  int64_t min_piece = 0, piece = 0;  // gather piece length (nonzeros): lower bound, target
+  bool iperm = true;                 // reduce index stream (else perm)
+  bool aligned = false;              // segments padded to 16 B
+  bool supported = true;             // false: this build cannot make the layout (device build, aligned)
+  int cut = 0;                       // chunk-cut window
+  int ranges = 0;                    // cache-sized ranges wanted (≤ 1: none)
+  bool own_cuts = false;             // … as `ranges` nnz-balanced row cuts of the plan's own (lhpc_csr_partition_rows)
+  bool pre = false;                  // phase-A tables
+  int steps = 8;                     // gather steps in flight
+  // by the plan's final range count K (user splits + 1, or the accepted cuts
+  // + 1; ≤ 1: no ranges):
+  bool ring(int K) const { return K > 1 && ring_ok; }
+  bool nt(int K) const { return store != LHPC_STORE_AUTO ? store == LHPC_STORE_NT : K <= 1 && past_cache; }
+  int64_t range_piece(int K) const;
+  // inputs of the three above
+  bool ring_ok = false, past_cache = false;
+  int store = LHPC_STORE_AUTO, cus = 256;
+  int64_t nnz = 0, range_piece_opt = 0;
+};
+XtilePolicy xtile_policy(const XtileShape &s, const lhpc_options &o);
+
 // The phases of build_xtile, so that the O(nnz) passes can also run on the
-// GPU from device-resident input (lhpc_xtile_device.hip) while everything that
-// decides the layout stays this one host code:
+// GPU from device-resident input (layout_device of lhpc_spmv_xtile.hip) while
+// everything that decides the layout stays this one host code:
 //   xtile_plan_chunks      validation, chunk cuts (ce, cr), ranges, cont; needs
 //                          col only for unit > 1; zeroes segoff
 //   (counts)               segoff row c+1 = count of chunk c per tile
@@ -161,8 +223,12 @@ inline int64_t xtile_wave_pos(int64_t i, int run, int vw) {
   return w * 64 * run + (q * 64 + l) * vw + r;
 }
 
-// Per-chunk region bases (vbase[c]: chunk c's positions start there, each
-// chunk padded to whole wave regions of 64·run positions; vbase[C] = total)
+// Per-chunk region bases of that layout alone (vbase[c]: chunk c's positions
+// start there, each chunk padded to whole wave regions of 64·run positions;
+// vbase[C] = total).  LHPC_ERR_UNSUPPORTED if vbase[C] + tail ≥ 2^31.
+int xtile_run_bases(const XtileHost &o, int run, int64_t tail, std::vector<int32_t> &vbase);
+
+// The region bases (xtile_run_bases)
 // and the val (tsz bytes each) and, when o.iperm is set, iperm streams in
 // the wave-transposed layout; val padding is 0, iperm padding is M (the
 // reduce keeps x = 0 in LDS slot M, so a padded position needs no mask).  Extra `tail` entries

@@ -168,38 +168,14 @@ int launch(const lhpc_spmv_plan *p, const void *x, void *y, hipStream_t s) {
   return csr_launch(p, x, y, s);
 }
 
-// XTILE column blocks (lhpc_options.xtile_col_blocks).  A reduce chunk holds
-// M nonzeros and meets every one of the S tiles, so its segment per tile is
-// M/S nonzeros: 32 for C2 (S = 256), 4 at n = 80M (S = 2048), and the
-// reduce's cost per nonzero grows with S (DESIGN.md §4 "large n": 632 GFLOP/s
-// at S = 256, 533 at 768, 408 at 1024, 244 at 2048).  Cutting the columns into
-// B blocks gives each block's plan S/B tiles; the blocks run in turn on x's
-// column ranges, every block after the first adding into y.  A chunk also
-// holds ≤ M/8 rows, so as a block's rows get shorter its chunks shrink with
-// the blocks.  Same box, fp32 15 per row, forced B (profiles/r04/col_blocks):
-// n = 10M (256 tiles) B = 1 / 2: 601 / 534 GFLOP/s; 40M (1024) B = 2 / 3 /
-// 4: 498 / 446 / 426; 80M (2048) B = 2 / 3 / 4 / 6: 378 / 417 / 365 / 314;
-// 150M (3840, two row parts) B = 2 / 3 / 4: 316 / 371 / 342.  fp64 10M (489)
-// B = 1 / 2: 318 / 304; 40M (1954) B = 2 / 3 / 4 / 6: 264 / 261 / 230 / 180.
-// Hence B = ⌈S / 768⌉, at most mean row length / 5.
-constexpr int64_t kColBlockTiles = 768;
-int xtile_col_blocks_for(int64_t n_rows, int64_t n_cols, int64_t nnz, size_t tsz, const lhpc_options &o) {
-  const int64_t most = std::max<int64_t>(1, n_cols / 64);  // ≥ 64 columns per block
-  if (o.xtile_col_blocks > 0) return static_cast<int>(std::min<int64_t>(o.xtile_col_blocks, most));
-  const int64_t W = tsz == 4 ? 40960 : 20480, S = (n_cols + W - 1) / W;
-  if (S <= kColBlockTiles || n_rows <= 0) return 1;
-  const double mean = static_cast<double>(nnz) / static_cast<double>(n_rows);
-  const int64_t bmax = std::max<int64_t>(1, static_cast<int64_t>(mean / 5.0));
-  return static_cast<int>(std::min({(S + kColBlockTiles - 1) / kColBlockTiles, bmax, most}));
-}
-
 // XTILE row parts: the tile stream of one plan is addressed with int32
 // offsets (nnz + 8 padding entries per tile < 2^31, lhpc_plan.cpp
 // build_xtile).  A larger matrix (n ≳ 143M rows at 15 nonzeros per row) is
 // cut into nnz-balanced row parts of ≤ cap nonzeros, each an ordinary XTILE
 // plan over its rows (row_ptr rebased, the caller's col/val at the part's
 // offset) run in turn on the same x, instead of dropping to XSLICE.  With
-// B > 1 column blocks every row part is further cut by column (above).
+// B > 1 column blocks every row part is further cut by column (lhpc_plan.cpp
+// xtile_partition_policy).
 // LHPC_ERR_UNSUPPORTED when some single row exceeds the cap.
 // d_rp non-null: device input (col_idx / val and d_rp in HBM, rp a host copy
 // of row_ptr): every part's layout is built on the GPU (xtile_build_device).
@@ -427,14 +403,11 @@ int plan_create_impl(lhpc_spmv_plan **out, int dtype, int64_t n_rows, int64_t n_
   // options.spmv_no_xtile selects XSLICE instead.
   const bool want_xtile = (flags & LHPC_PLAN_FORCE_XTILE) || (nolocal && !o.spmv_no_xtile);
   if (want_xtile && n_rows > 0) {
-    // row parts when the tile stream outgrows its int32 offsets (or a lower
-    // cap is asked for); user row splits keep a single plan
-    // and column blocks when x spans many tiles (xtile_col_blocks_for)
-    const int64_t tiles = (n_cols + (tsz == 4 ? 40960 : 20480) - 1) / (tsz == 4 ? 40960 : 20480);
-    int64_t cap = INT32_MAX - 8 * (tiles + 256) - (int64_t{1} << 16);
-    if (o.xtile_part_nnz > 0) cap = std::min<int64_t>(cap, o.xtile_part_nnz);
-    const int B = n_splits == 0 ? xtile_col_blocks_for(n_rows, n_cols, nnz, tsz, o) : 1;
-    const bool parts = (nnz > cap || B > 1) && n_splits == 0 && (tiles + B - 1) / B <= 4096;
+    // row parts and column blocks, or one plan (lhpc_plan.hpp xtile_partition_policy)
+    const XtilePartition pp = xtile_partition_policy(n_rows, n_cols, nnz, tsz, n_splits, o);
+    const int64_t cap = pp.cap;
+    const int B = pp.col_blocks;
+    const bool parts = pp.parts;
     // the layout is built on the GPU from uploaded copies of A (byte-identical
     // to the host build, DESIGN.md §4 device input; C2 0.57 → ≈ 0.15 s); the
     // host build when the device cannot (aligned segments, no memory)
@@ -620,14 +593,15 @@ int plan_create_device_input(lhpc_spmv_plan **out, int dtype, int64_t n_rows, in
   const double locality_thr = o.spmv_locality > 0 ? o.spmv_locality : 0.25;
   const bool auto_ok = !(flags & (LHPC_PLAN_FORCE_ROWGROUP | LHPC_PLAN_FORCE_ADAPTIVE | LHPC_PLAN_FORCE_XSLICE |
                                    LHPC_PLAN_FORCE_XTILE | LHPC_PLAN_FORCE_SELL));
-  const int64_t tiles = (n_cols + (tsz == 4 ? 40960 : 20480) - 1) / (tsz == 4 ? 40960 : 20480);
-  int64_t cap = INT32_MAX - 8 * (tiles + 256) - (int64_t{1} << 16);
-  if (o.xtile_part_nnz > 0) cap = std::min<int64_t>(cap, o.xtile_part_nnz);
-  // row parts and column blocks as plan_create_impl chooses them
-  const int B = n_splits == 0 ? xtile_col_blocks_for(n_rows, n_cols, nnz, tsz, o) : 1;
-  const bool parts = (nnz > cap || B > 1) && n_splits == 0;
+  // row parts and column blocks as plan_create_impl chooses them; what parts
+  // cannot hold, or one plan cannot (the host path's xtile_build would refuse
+  // it, or build it whole under user splits), is left to the host path
+  const XtilePartition pp = xtile_partition_policy(n_rows, n_cols, nnz, tsz, n_splits, o);
+  const int64_t cap = pp.cap;
+  const int B = pp.col_blocks;
+  const bool parts = pp.parts;
   const bool single = n_devices <= 1 && !o.multi_force && n_rows > 0 &&
-                      (parts ? (tiles + B - 1) / B <= 4096 : nnz <= cap && tiles <= 4096);
+                      (parts || (nnz <= cap && pp.tiles <= kXtMaxTiles));
   bool want_xtile = single && (flags & LHPC_PLAN_FORCE_XTILE);
   // the host path's locality test (plan_create_impl's `nolocal`), on
   // device-fetched samples: XTILE here, and the SELL decision below

@@ -64,7 +64,10 @@ struct lhpc_spmv_plan {
   std::vector<int64_t> split_rows, xt_srow, xt_src, xt_sco;
   int32_t *d_cdesc = nullptr;
   int32_t *d_cr = nullptr, *d_seghi = nullptr, *d_pieces = nullptr, *d_cont = nullptr;
-  uint32_t *d_seg = nullptr;  // segment table (lhpc_plan.hpp xtile_segment_table)
+  // segment table (lhpc_plan.hpp xtile_segment_table: d_seg, d_seghi); a plan
+  // with xt_pre keeps the reduce's phase-A tables there instead
+  // (xtile_phase_tables: d_seg = bt, d_seghi = base_ne)
+  uint32_t *d_seg = nullptr;
   uint16_t *d_col16 = nullptr, *d_perm = nullptr;
   int xt_p = 1;  // reduce: 1 perm scatter, 3 iperm gather (DESIGN.md §4 XTILE)
   int xt_al = 0;  // aligned segments: 16-B units (lhpc_options.xtile_align)
@@ -74,8 +77,8 @@ struct lhpc_spmv_plan {
   // range; per piece {ring delta, flags} in d_pext; range k's segment-table hi
   // rows start at xt_hrow[k]
   int xt_ring = 0;
-  int xt_pre = 0;
-  int64_t xt_seg_n = 0, xt_seghi_n = 0;  // entries of d_seg / d_seghi  // the reduce reads the plan's phase-A tables (d_seg = bt, d_seghi = base_ne)
+  int xt_pre = 0;                         // the reduce reads the plan's phase-A tables (lhpc_options.xtile_pretable)
+  int64_t xt_seg_n = 0, xt_seghi_n = 0;  // entries of d_seg / d_seghi
   int64_t xt_ring_len = 0;
   int32_t *d_pext = nullptr;
   std::vector<int64_t> xt_hrow;

@@ -27,9 +27,7 @@ namespace {
 
 constexpr int kXtGatherBlock = 1024;  // gather: 16 waves per CU, one tile of x in LDS
 constexpr int kXtFixBlock = 256;      // fix-up
-template <typename T> struct XtTile;
-template <> struct XtTile<float> { static constexpr int W = 40960; };   // 160 KB
-template <> struct XtTile<double> { static constexpr int W = 20480; };  // 160 KB
+template <typename T> struct XtTile { static constexpr int W = static_cast<int>(xtile_capacity(sizeof(T))); };  // 160 KB
 
 // gather: block b streams pieces[3b..3b+1] of tile pieces[3b+2]; 8 nonzeros
 // per thread and step (one 16-B col16 load, 8 LDS gathers, 8 contiguous xg
@@ -1015,210 +1013,179 @@ __global__ __launch_bounds__(64) void k_xt_permute_blocks(const int32_t *__restr
   }
 }
 
-// dev: col_idx and val are device pointers (LHPC_PLAN_DEVICE_INPUT; rp is a
-// host copy of row_ptr): the O(nnz) passes run on the GPU
+// ------------------------------------------------------------- plan build
+// Three stages (build_t): policy — every decision, lhpc_plan.hpp xtile_policy;
+// layout — the host tables (XtileHost, run bases) and the plan's O(nnz)
+// streams in HBM (d_val, d_col16, d_perm), by host passes (layout_host) or
+// from device-resident col / val (layout_device); upload — the tables and
+// scalars, the same for both.
 template <typename T>
-int build_t(lhpc_spmv_plan *p, RowPtrView rp, const int32_t *col_idx, const void *val, bool dev) {
-  constexpr size_t tsz = sizeof(T);
-  constexpr int M = XtRed<T, xt_red_blk<T>()>::M, RMAX = XtRed<T, xt_red_blk<T>()>::Rmax, RUN = xt_run<T>();
-  int cus = 256;
-  hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, p->device) == hipSuccess) cus = prop.multiProcessorCount;
-  // tile width: the LDS capacity XtTile<T>::W, narrowed for fp32 so that the
-  // tile count is a whole multiple of the CUs when that adds ≤ 10% tiles
-  // (C2: 245 → 256 tiles of 39063 columns): a cache-sized range's gather
-  // round of one piece per tile then fills every CU.  fp64 (single range,
-  // ≈ 2 pieces per CU) lost 3% with it (C3 489 → 512 tiles: 0.913 → 0.941 ms)
-  int64_t W = XtTile<T>::W;
-  {
-    const int64_t s0 = (p->n_cols + W - 1) / W, s1 = (s0 + cus - 1) / cus * cus;
-    // (never past build_xtile's 4096-tile cap: on a CU count that does not
-    // divide 4096 the rounding could otherwise cost a plan its XTILE layout)
-    bool narrow = sizeof(T) == 4 && s1 * 10 <= s0 * 11 && s1 <= 4096;
-    if (const char *e = tuning_env("LHPC_XTILE_TW")) narrow = std::atoi(e) != 0;
-    if (narrow && s1 > s0) W = (p->n_cols + s1 - 1) / s1;
-  }
-  // ≈ 2 gather workgroups per CU (one resident per CU: 160 KB of LDS each)
-  // and ≥ 4 tiles' worth of stream per piece, so the tile load (W·T bytes)
-  // stays ≤ 1/4 of a piece's col16 + xg traffic on small (per-rank) matrices
-  const int64_t min_piece = 4 * W * static_cast<int64_t>(tsz) / (2 + static_cast<int64_t>(tsz));
-  int64_t piece = std::max<int64_t>(min_piece, p->nnz / (2 * static_cast<int64_t>(cus)) + 1);
-  const lhpc_options &o = p->opt;
-  if (o.xtile_piece > 0) piece = std::max<int64_t>(8, o.xtile_piece);
-  // reduce index stream: iperm (gather each CSR position's x from the flat
-  // segment concatenation in LDS), else perm (scatter into CSR slots).  Round
-  // 1 kept perm below 32 full chunks per CU (per-rank matrices at N ≥ 4);
-  // with the reduce as it is now iperm is as fast or faster there too — same
-  // box, local work of rank 0 (tools/explore_rank_reduce.py,
-  // profiles/r04/rank_reduce.jsonl): fp32 W = 4 0.132 → 0.118 ms, W = 8
-  // 0.0656 → 0.0653; fp64 W = 4 0.263 → 0.245, W = 8 0.125 → 0.118
-  bool ip = true;
-  if (o.xtile_reduce != LHPC_XTILE_REDUCE_AUTO) ip = o.xtile_reduce == LHPC_XTILE_REDUCE_IPERM;
-  // the iperm reduce addresses xg with 32-bit buffer offsets: stream + tile
-  // padding (≤ 8 per tile) + one piece of slack must stay below 2 GiB
-  const int64_t n_tiles = (p->n_cols + W - 1) / W;
-  const int64_t stream_max = p->nnz + 8 * n_tiles + 2 * M;
-  if (stream_max * static_cast<int64_t>(tsz) >= (int64_t{1} << 31)) ip = false;
-  p->xt_p = ip ? 3 : 1;
-  // aligned segments (iperm only): each (tile, chunk) segment padded to 16 B
-  // (≤ VW − 1 entries per segment, ≤ 3 per 4 nonzeros in the worst case)
-  constexpr int VW = static_cast<int>(16 / tsz);
-  bool al = false;
-  if (o.xtile_align == LHPC_XTILE_ALIGN_UNITS) al = true;
-  if (al && (!ip || (stream_max + (VW - 1) * std::min<int64_t>(p->nnz, n_tiles * (p->nnz / (M / 2) + 2))) *
-                                static_cast<int64_t>(tsz) >= (int64_t{1} << 31)))
-    al = false;
-  // the fp32 aligned reduce with 8 segment-table entries per thread (S > 2048
-  // tiles, n_cols > 84M) would spill a VGPR: packed segments there
-  if (al && xtile_g<T>(static_cast<int>(std::min<int64_t>(n_tiles, 4096))) > 4) al = false;
-  p->xt_al = al ? 1 : 0;
-  // chunk cuts: at the last row start in the back M/32 of the window, else
-  // mid-row (the row's pieces meet in k_xtile_fixup).  Per-chunk costs are
-  // fixed, so full chunks matter on skewed rows: C4 has 19803 chunks when any
-  // row start in the back half is taken, 18454 with the back M/32 (C2: 18316
-  // either way); options.xtile_cut overrides (entries, 1..M)
-  int cut = M / 32;
-  if (o.xtile_cut > 0) cut = std::min(M, o.xtile_cut);
-  // cache-sized ranges: K nnz-balanced row ranges, gathered and reduced in
-  // turn, so that each range's xg (≈ 200 MB) is still in the 256 MB Infinity
-  // Cache when its reduce reads it back.  fp32 only: each extra range re-reads
-  // x (n_cols·T) in its gather.  Same box: C2 reduce 352 → 295
-  // µs, gather 163 → 179 µs, call 523.5 → 483.8 µs at K = 3 (K = 4: 506.7);
-  // C3 (fp64, K = 6: 200 MB ranges) 928 → 944 µs, so not for fp64 — until
-  // the xg ring (round 6, same box, xtile_ranges = 1 / 3 / 4 / 6 / 8: C3
-  // 0.908 / 0.943 / 0.995 / 0.868 / 0.902 ms): fp64 takes the ranges when its
-  // plan can hold the ring (no user row splits, iperm reduce).
-  // Only while each range still streams ≥ min_piece nonzeros per tile (fp64:
-  // min_piece / 2 — its ring saves the 8-B xg write-back) and K ≤ 8: every
-  // range re-loads all S tiles of x, so a wide x (n = 80M: 1954 tiles; n =
-  // 150M: 3662) would spend more on tile loads than the cache saves — such
-  // plans keep one range (the n = 150M plan took 23.6 ms with 8 ranges per part)
-  int mall = 0;
-  {
-    const int64_t xg_bytes = p->nnz * static_cast<int64_t>(tsz);
-    const int64_t k = (xg_bytes + (int64_t{200} << 20) - 1) / (int64_t{200} << 20);
-    const int64_t tiles = (p->n_cols + W - 1) / W;
-    // the xg ring: the plan's own cache ranges by default; user row ranges
-    // only when asked for (xtile_ring = 2: the library's per-rank plans,
-    // which gather and reduce range by range in order)
-    const bool ring_ok = ip && !al && (p->split_rows.empty() ? o.xtile_ring != 1 : o.xtile_ring == 2);
-    const int64_t need = tsz == 4 ? min_piece : min_piece / 2;
-    if ((tsz == 4 || ring_ok) && xg_bytes > (int64_t{256} << 20) && k <= 8 &&
-        p->nnz / k / std::max<int64_t>(1, tiles) >= need)
-      mall = static_cast<int>(k);
-  }
-  if (o.xtile_ranges > 0) mall = o.xtile_ranges;
-  // a row-range plan (user splits) whose xg exceeds the cache gets per-range
-  // gather pieces for its own ranges (stage still gathers them all)
-  const bool user_splits = !p->split_rows.empty();
-  if (!p->split_rows.empty() && mall > 1) p->xt_mall = static_cast<int>(p->split_rows.size()) + 1;
-  if (p->split_rows.empty() && mall > 1 && p->n_rows >= 2LL * mall) {
-    std::vector<int64_t> cuts(static_cast<size_t>(mall) + 1);
-    LHPC_TRY(lhpc_csr_partition_rows(rp.p, rp.bits, p->n_rows, mall, cuts.data()));
-    for (int k = 1; k < mall; ++k)
-      if (cuts[k] > 0 && cuts[k] < p->n_rows && (p->split_rows.empty() || cuts[k] > p->split_rows.back()))
-        p->split_rows.push_back(cuts[k]);
-    p->xt_mall = static_cast<int>(p->split_rows.size()) + 1;
-  }
+struct XtBuild {
+  static constexpr size_t tsz = sizeof(T);
+  static constexpr int M = XtRed<T, xt_red_blk<T>()>::M, RMAX = XtRed<T, xt_red_blk<T>()>::Rmax, RUN = xt_run<T>();
+  static constexpr int VW = static_cast<int>(16 / tsz);
+  lhpc_spmv_plan *p;
+  const XtilePolicy &pol;
+  RowPtrView rp;
   XtileHost xt;
-  // device-side O(nnz) buffers (dev only): chunk starts, segment starts, run bases
+  std::vector<int32_t> vbase;  // run bases (xtile_run_bases)
+  size_t nrun = 0;             // positions of the val / iperm runs, one region of padding included
+
+  int up(void *d, const void *h, size_t n) {
+    LHPC_TRY(dmalloc(static_cast<void **>(d), n, p->bytes));
+    if (n && h) LHPC_HIP_TRY(hipMemcpy(*static_cast<void **>(d), h, n, hipMemcpyHostToDevice));
+    return LHPC_OK;
+  }
+  const int64_t *splits() const { return p->split_rows.data(); }
+  int n_splits() const { return static_cast<int>(p->split_rows.size()); }
+
+  // the gather pieces of a plan with ranges, per range (both layouts, once
+  // segoff and rchunk stand and before col16 is permuted by piece)
+  void range_pieces() {
+    if (p->xt_mall <= 1) return;
+    const int64_t rpn = pol.range_piece(p->xt_mall);
+    p->xt_ring = pol.ring(p->xt_mall) ? 1 : 0;
+    if (p->xt_ring) {
+      xtile_ring_pieces(xt, rpn, p->xt_rpc);
+      p->xt_ring_len = xt.ring_len;
+      p->xt_hrow = xt.hrow;
+    } else {
+      xtile_range_pieces(xt, rpn, p->xt_rpc);
+    }
+  }
+  // perm reduce: one entry per stream position and one sentinel entry past
+  // the stream: the reduce loads it for positions past m, and its perm is
+  // the spare LDS slot M
+  int alloc_perm() {
+    LHPC_TRY(up(&p->d_perm, nullptr, static_cast<size_t>(xt.total + 2) * 2));
+    const uint16_t spare[2] = {static_cast<uint16_t>(M), static_cast<uint16_t>(M)};
+    LHPC_HIP_TRY(hipMemcpy(p->d_perm + xt.total, spare, 4, hipMemcpyHostToDevice));
+    return LHPC_OK;
+  }
+
+  int layout_host(const int32_t *col_idx, const void *val) {
+    LHPC_TRY(build_xtile(rp.p, rp.bits, col_idx, p->n_rows, p->n_cols, pol.W, M, RMAX, pol.piece,
+                         static_cast<int>(tsz), splits(), n_splits(), pol.iperm, pol.cut, xt, pol.aligned ? VW : 1));
+    // val (and iperm) in the wave-transposed run layout, each chunk padded to
+    // whole wave regions, plus one region of zeros (an empty chunk reads it)
+    std::unique_ptr<unsigned char[]> valt;
+    std::unique_ptr<uint16_t[]> ipt;
+    LHPC_TRY(xtile_transpose_runs(xt, val, tsz, RUN, 64 * RUN, vbase, valt, ipt));
+    nrun = static_cast<size_t>(vbase[xt.n_chunks]) + 64 * RUN;
+    LHPC_TRY(up(&p->d_val, valt.get(), nrun * tsz));
+    valt.reset();
+    range_pieces();
+    xtile_permute_gather_blocks(xt, VW);
+    LHPC_TRY(up(&p->d_col16, xt.col16.get(), static_cast<size_t>(xt.total) * 2));
+    if (pol.iperm) return up(&p->d_perm, ipt.get(), nrun * 2);
+    LHPC_TRY(alloc_perm());
+    if (xt.total)
+      LHPC_HIP_TRY(hipMemcpy(p->d_perm, xt.perm.get(), static_cast<size_t>(xt.total) * 2, hipMemcpyHostToDevice));
+    return LHPC_OK;
+  }
+
+  // layout_device's temporaries in HBM: chunk starts, per-chunk tile counts,
+  // segment starts, run bases, pieces.  Members, freed with the build: freed
+  // ahead of the upload stage's allocations they cost a C2 build 15 of its 75 ms
   struct DevTmp {
     void *a = nullptr;
     ~DevTmp() {
       if (a) (void)hipFree(a);
     }
-  } d_ce, d_segoff, d_vbase, d_counts;
-  if (dev) {
-    if (al) return LHPC_ERR_UNSUPPORTED;  // aligned segments: host build only
+    int put(const void *h, size_t n) {
+      LHPC_HIP_TRY(hipMalloc(&a, n));
+      if (h) LHPC_HIP_TRY(hipMemcpy(a, h, n, hipMemcpyHostToDevice));
+      return LHPC_OK;
+    }
+    const int32_t *i32() const { return static_cast<const int32_t *>(a); }
+  } d_ce, d_counts, d_segoff, d_vbase, d_pieces;
+  // col_idx and val are device pointers (LHPC_PLAN_DEVICE_INPUT; rp is a host
+  // copy of row_ptr): the O(nnz) passes run on the GPU, every decision in the
+  // host code of lhpc_plan.cpp, fed the counts of k_xt_counts
+  int layout_device(const int32_t *col_idx, const void *val) {
+    const int64_t W = pol.W;
     LHPC_TRY(xtile_plan_chunks(rp.p, rp.bits, nullptr, p->n_rows, p->n_cols, W, M, RMAX, static_cast<int>(tsz),
-                               p->split_rows.data(), static_cast<int>(p->split_rows.size()), ip, cut, xt, 1));
-    const int64_t S = xt.S, C = xt.n_chunks;
+                               splits(), n_splits(), pol.iperm, pol.cut, xt, 1));
+    const int S = xt.S;
+    const unsigned C = static_cast<unsigned>(xt.n_chunks);
     if (S > kXtBuildMaxS) return LHPC_ERR_UNSUPPORTED;
-    LHPC_HIP_TRY(hipMalloc(&d_ce.a, xt.ce.size() * 4));
-    LHPC_HIP_TRY(hipMemcpy(d_ce.a, xt.ce.data(), xt.ce.size() * 4, hipMemcpyHostToDevice));
+    LHPC_TRY(d_ce.put(xt.ce.data(), xt.ce.size() * 4));
     if (C > 0) {
-      LHPC_HIP_TRY(hipMalloc(&d_counts.a, static_cast<size_t>(C * S) * 4));
-      hipLaunchKernelGGL(k_xt_counts, dim3(static_cast<unsigned>(C)), dim3(256), 0, nullptr,
-                         static_cast<const int32_t *>(d_ce.a), col_idx, W, static_cast<int>(S),
+      const size_t nc = static_cast<size_t>(C) * S * 4;
+      LHPC_TRY(d_counts.put(nullptr, nc));
+      hipLaunchKernelGGL(k_xt_counts, dim3(C), dim3(256), 0, nullptr, d_ce.i32(), col_idx, W, S,
                          static_cast<int32_t *>(d_counts.a));
       LHPC_HIP_TRY(hipGetLastError());
-      LHPC_HIP_TRY(hipMemcpy(xt.segoff.data() + S, d_counts.a, static_cast<size_t>(C * S) * 4, hipMemcpyDeviceToHost));
+      LHPC_HIP_TRY(hipMemcpy(xt.segoff.data() + S, d_counts.a, nc, hipMemcpyDeviceToHost));
     }
     std::vector<int64_t> tbase;
     LHPC_TRY(xtile_plan_offsets(xt, tbase));
-    xtile_plan_pieces(xt, tbase, piece);
-  } else {
-    LHPC_TRY(build_xtile(rp.p, rp.bits, col_idx, p->n_rows, p->n_cols, W, M, RMAX, piece, static_cast<int>(tsz),
-                         p->split_rows.data(), static_cast<int>(p->split_rows.size()), ip, cut, xt, al ? VW : 1));
-  }
-  p->kernel = LHPC_KERNEL_XTILE;
-  p->rp64 = 0;
-  p->S = xt.S;
-  p->xs_width = W;
-  p->xt_C = xt.n_chunks;
-  p->xt_pieces = static_cast<int64_t>(xt.pieces.size() / 3);
-  p->xt_cont = static_cast<int64_t>(xt.cont.size());
-  p->xt_total = xt.total;
-  // phase-A tables (options.xtile_pretable): iperm
-  // plans without aligned segments, G = 1.  Default for fp64 only — same box,
-  // two runs each: C3 reduce 89.9 → 85.3 µs per range (its 16-wave scan was
-  // 2.3K of 27.8K cycles per chunk), C2 88.1 → 89.4 µs (the tables' extra
-  // 2 KB per chunk outweigh an 8-wave scan)
-  const bool pre = ip && !al && xtile_g<T>(xt.S) == 1 &&
-                   (o.xtile_pretable == 2 || (o.xtile_pretable == 0 && sizeof(T) == 8));
-  p->xt_pre = pre ? 1 : 0;
-  p->xt_lds = xtile_lds_bytes_g<T>(xt.S, xtile_g<T>(xt.S), pre);
-#ifdef LHPC_XT_LDS_TOTAL  // A/B build only: reduce blocks padded to this many bytes of LDS (fewer per CU)
-  if (sizeof(T) == 4) p->xt_lds = std::max<size_t>(p->xt_lds, LHPC_XT_LDS_TOTAL);
-#endif
-  if (o.xtile_steps > 0) {
-    const int u = o.xtile_steps;
-    p->xt_u = u <= 2 ? 2 : u < 8 ? 4 : u < 16 ? 8 : 16;
-  }
-  // non-temporal xg stores when the xg of a single-range plan exceeds the 256
-  // MB Infinity Cache anyway (same box, two runs each: C3 918.6 → 908.8 µs
-  // median); cache-sized ranges need their xg to stay there (C2 with them
-  // non-temporal: 473 → 536 µs)
-  p->xt_nt = p->xt_mall <= 1 && p->nnz * static_cast<int64_t>(tsz) > (int64_t{256} << 20) ? 1 : 0;
-  if (o.xtile_store != LHPC_STORE_AUTO) p->xt_nt = o.xtile_store == LHPC_STORE_NT ? 1 : 0;
-  const void *rfn = xtile_reduce_fn<T>(xtile_g<T>(xt.S), ip, al, pre);
-  if (!rfn) return LHPC_ERR_UNSUPPORTED;  // more tiles than the reduce's segment table holds
-  LHPC_HIP_TRY(hipFuncSetAttribute(rfn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(p->xt_lds)));
-  const int64_t n_rows = p->n_rows, C = xt.n_chunks;
-  auto up = [&](void **d, const void *h, size_t n) -> int {
-    LHPC_TRY(dmalloc(d, n, p->bytes));
-    if (n && h) LHPC_HIP_TRY(hipMemcpy(*d, h, n, hipMemcpyHostToDevice));
-    return LHPC_OK;
-  };
-  std::vector<int32_t> rp32(static_cast<size_t>(n_rows + 1));
-  for (int64_t i = 0; i <= n_rows; ++i) rp32[static_cast<size_t>(i)] = static_cast<int32_t>(rp[i]);
-  LHPC_TRY(up(&p->d_row_ptr, rp32.data(), rp32.size() * 4));
-  // val (and iperm) in the wave-transposed run layout, each chunk padded to
-  // whole wave regions, plus one region of zeros (an empty chunk reads it)
-  std::vector<int32_t> vbase;
-  std::unique_ptr<unsigned char[]> valt;
-  std::unique_ptr<uint16_t[]> ipt;
-  size_t nrun = 0;
-  if (dev) {
-    // run bases as xtile_transpose_runs; the runs themselves come from
-    // k_xt_scatter (val zero-padded, iperm padded with the zero slot M)
-    std::vector<int64_t> vb(static_cast<size_t>(C) + 1, 0);
-    const int64_t reg = 64 * RUN;
-    for (int64_t c = 0; c < C; ++c) vb[c + 1] = vb[c] + (xt.ce[c + 1] - xt.ce[c] + reg - 1) / reg * reg;
-    if (vb[C] + reg >= INT32_MAX) return LHPC_ERR_UNSUPPORTED;
-    vbase.assign(vb.begin(), vb.end());
+    xtile_plan_pieces(xt, tbase, pol.piece);
+    // the runs themselves come from k_xt_scatter (val zero-padded, iperm
+    // padded with the zero slot M)
+    LHPC_TRY(xtile_run_bases(xt, RUN, 64 * RUN, vbase));
     nrun = static_cast<size_t>(vbase[C]) + 64 * RUN;
-    p->xt_nrun = static_cast<int64_t>(nrun);
-    LHPC_TRY(dmalloc(&p->d_val, nrun * tsz, p->bytes));
+    LHPC_TRY(up(&p->d_val, nullptr, nrun * tsz));
     LHPC_HIP_TRY(hipMemset(p->d_val, 0, nrun * tsz));
-  } else {
-    LHPC_TRY(xtile_transpose_runs(xt, val, tsz, RUN, 64 * RUN, vbase, valt, ipt));
-    nrun = static_cast<size_t>(vbase[C]) + 64 * RUN;
-    p->xt_nrun = static_cast<int64_t>(nrun);
-    LHPC_TRY(up(&p->d_val, valt.get(), nrun * tsz));
-    valt.reset();
+    range_pieces();
+    // col16 and perm / iperm + val runs on the device, then the gather-store
+    // permutation of col16 inside every piece
+    LHPC_TRY(up(&p->d_col16, nullptr, static_cast<size_t>(xt.total) * 2));
+    LHPC_HIP_TRY(hipMemset(p->d_col16, 0, static_cast<size_t>(std::max<int64_t>(xt.total, 1)) * 2));
+    if (pol.iperm) {
+      LHPC_TRY(up(&p->d_perm, nullptr, nrun * 2));
+      LHPC_HIP_TRY(hipMemsetD16(reinterpret_cast<hipDeviceptr_t>(p->d_perm), static_cast<unsigned short>(M), nrun));
+    } else {
+      LHPC_TRY(alloc_perm());
+      LHPC_HIP_TRY(hipMemset(p->d_perm, 0, static_cast<size_t>(xt.total) * 2));
+    }
+    const size_t np = xt.pieces.size() / 3;
+    if (np) LHPC_TRY(d_pieces.put(xt.pieces.data(), xt.pieces.size() * 4));  // before the launches: a copy would wait for them
+    if (C > 0) {
+      LHPC_TRY(d_segoff.put(xt.segoff.data(), xt.segoff.size() * 4));
+      LHPC_TRY(d_vbase.put(vbase.data(), vbase.size() * 4));
+      int sbits = 0;
+      while ((int64_t{1} << sbits) < S) ++sbits;
+      const auto scatter = pol.iperm ? k_xt_scatter<T, true> : k_xt_scatter<T, false>;
+      hipLaunchKernelGGL(scatter, dim3(C), dim3(64), 0, nullptr, d_ce.i32(), d_segoff.i32(), d_vbase.i32(), col_idx,
+                         static_cast<const T *>(val), W, S, sbits, p->d_col16, pol.iperm ? nullptr : p->d_perm,
+                         pol.iperm ? p->d_perm : nullptr, static_cast<T *>(p->d_val));
+      LHPC_HIP_TRY(hipGetLastError());
+    }
+    if (np) {
+      hipLaunchKernelGGL(k_xt_permute_blocks, dim3(static_cast<unsigned>(np)), dim3(64), 0, nullptr, d_pieces.i32(),
+                         VW, p->d_col16);
+      LHPC_HIP_TRY(hipGetLastError());
+    }
+    LHPC_HIP_TRY(hipDeviceSynchronize());
+    return LHPC_OK;
   }
-  {
+
+  // the plan's scalars and tables from the layout
+  int upload() {
+    const int64_t n_rows = p->n_rows, C = xt.n_chunks;
+    p->kernel = LHPC_KERNEL_XTILE;
+    p->rp64 = 0;
+    p->S = xt.S;
+    p->xs_width = pol.W;
+    p->xt_C = C;
+    p->xt_pieces = static_cast<int64_t>(xt.pieces.size() / 3);
+    p->xt_cont = static_cast<int64_t>(xt.cont.size());
+    p->xt_total = xt.total;
+    p->xt_nrun = static_cast<int64_t>(nrun);
+    p->xt_pre = pol.pre ? 1 : 0;
+    p->xt_u = pol.steps;
+    p->xt_nt = pol.nt(p->xt_mall) ? 1 : 0;
+    p->xt_lds = xtile_lds_bytes_g<T>(xt.S, xtile_g<T>(xt.S), pol.pre);
+#ifdef LHPC_XT_LDS_TOTAL  // A/B build only: reduce blocks padded to this many bytes of LDS (fewer per CU)
+    if (sizeof(T) == 4) p->xt_lds = std::max<size_t>(p->xt_lds, LHPC_XT_LDS_TOTAL);
+#endif
+    const void *rfn = xtile_reduce_fn<T>(xtile_g<T>(xt.S), pol.iperm, pol.aligned, pol.pre);
+    if (!rfn) return LHPC_ERR_UNSUPPORTED;  // more tiles than the reduce's segment table holds
+    LHPC_HIP_TRY(hipFuncSetAttribute(rfn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(p->xt_lds)));
+    std::vector<int32_t> rp32(static_cast<size_t>(n_rows + 1));
+    for (int64_t i = 0; i <= n_rows; ++i) rp32[static_cast<size_t>(i)] = static_cast<int32_t>(rp[i]);
+    LHPC_TRY(up(&p->d_row_ptr, rp32.data(), rp32.size() * 4));
     std::vector<int32_t> cd(static_cast<size_t>(8 * C + 8), 0);  // {e0, e1, r0, r1, vbase, 0, 0, 0}
     for (int64_t c = 0; c < C; ++c) {
       cd[8 * c] = xt.ce[c];
@@ -1227,125 +1194,86 @@ int build_t(lhpc_spmv_plan *p, RowPtrView rp, const int32_t *col_idx, const void
       cd[8 * c + 3] = xt.cr[c + 1];
       cd[8 * c + 4] = vbase[c];
     }
-    LHPC_TRY(up(reinterpret_cast<void **>(&p->d_cdesc), cd.data(), cd.size() * 4));
-  }
-  LHPC_TRY(up(reinterpret_cast<void **>(&p->d_cr), xt.cr.data(), xt.cr.size() * 4));
-  if (p->xt_mall > 1) {
-    // one gather round per range: ≈ one piece per (tile, range) part, so each
-    // range loads every tile once (only one 160-KB gather block fits a CU)
-    int64_t rpn = std::max<int64_t>(min_piece, p->nnz / p->xt_mall / static_cast<int64_t>(cus) * 5 / 4 + 1);
-    if (o.xtile_range_piece > 0) rpn = std::max<int64_t>(8, o.xtile_range_piece);
-    // the xg ring (options.xtile_ring): the plan's own cache
-    // ranges; user row ranges only with xtile_ring = 2 (lhpc_spmv_stage would
-    // gather every range into the one ring: a ring plan refuses it)
-    p->xt_ring = ip && !al && (user_splits ? o.xtile_ring == 2 : o.xtile_ring != 1) ? 1 : 0;
-    if (p->xt_ring) {
-      xtile_ring_pieces(xt, rpn, p->xt_rpc);
-      p->xt_ring_len = xt.ring_len;
-      p->xt_hrow = xt.hrow;
-    } else {
-      xtile_range_pieces(xt, rpn, p->xt_rpc);
+    LHPC_TRY(up(&p->d_cdesc, cd.data(), cd.size() * 4));
+    LHPC_TRY(up(&p->d_cr, xt.cr.data(), xt.cr.size() * 4));
+    LHPC_TRY(up(&p->d_pieces, xt.pieces.data(), xt.pieces.size() * 4));
+    if (p->xt_ring) LHPC_TRY(up(&p->d_pext, xt.pext.data(), xt.pext.size() * 4));
+    LHPC_TRY(up(&p->d_cont, xt.cont.data(), xt.cont.size() * 4));
+    {  // the segment table, or the reduce's phase-A tables in its place (seg = bt, seghi = base_ne)
+      std::vector<uint32_t> seg;
+      std::vector<int32_t> seghi;
+      (pol.pre ? xtile_phase_tables : xtile_segment_table)(xt, seg, seghi);
+      LHPC_TRY(up(&p->d_seg, seg.data(), seg.size() * 4));
+      LHPC_TRY(up(&p->d_seghi, seghi.data(), seghi.size() * 4));
+      p->xt_seg_n = static_cast<int64_t>(seg.size());
+      p->xt_seghi_n = static_cast<int64_t>(seghi.size());
     }
-    p->xt_pieces = static_cast<int64_t>(xt.pieces.size() / 3);
-  }
-  LHPC_TRY(up(reinterpret_cast<void **>(&p->d_pieces), xt.pieces.data(), xt.pieces.size() * 4));
-  if (p->xt_ring) LHPC_TRY(up(reinterpret_cast<void **>(&p->d_pext), xt.pext.data(), xt.pext.size() * 4));
-  LHPC_TRY(up(reinterpret_cast<void **>(&p->d_cont), xt.cont.data(), xt.cont.size() * 4));
-  if (dev) {
-    // col16 and perm / iperm + val runs on the device, then the gather-store
-    // permutation of col16 inside every piece
-    const int64_t S = xt.S;
-    LHPC_TRY(dmalloc(reinterpret_cast<void **>(&p->d_col16), static_cast<size_t>(xt.total) * 2, p->bytes));
-    LHPC_HIP_TRY(hipMemset(p->d_col16, 0, static_cast<size_t>(std::max<int64_t>(xt.total, 1)) * 2));
-    if (ip) {
-      LHPC_TRY(dmalloc(reinterpret_cast<void **>(&p->d_perm), nrun * 2, p->bytes));
-      LHPC_HIP_TRY(hipMemsetD16(reinterpret_cast<hipDeviceptr_t>(p->d_perm), static_cast<unsigned short>(M), nrun));
-    } else {
-      LHPC_TRY(dmalloc(reinterpret_cast<void **>(&p->d_perm), static_cast<size_t>(xt.total + 2) * 2, p->bytes));
-      LHPC_HIP_TRY(hipMemset(p->d_perm, 0, static_cast<size_t>(xt.total + 2) * 2));
-      const uint16_t spare[2] = {static_cast<uint16_t>(M), static_cast<uint16_t>(M)};
-      LHPC_HIP_TRY(hipMemcpy(p->d_perm + xt.total, spare, 4, hipMemcpyHostToDevice));
+    LHPC_TRY(up(&p->d_xg, nullptr, static_cast<size_t>((p->xt_ring ? xt.ring_len : xt.total) + 2) * tsz));
+    LHPC_TRY(up(&p->d_carry, nullptr, static_cast<size_t>(2 * C + 2) * 8));
+    LHPC_HIP_TRY(hipMemset(p->d_carry, 0, static_cast<size_t>(2 * C + 2) * 8));
+    if (!p->split_rows.empty()) {
+      const size_t K = p->split_rows.size() + 1;
+      p->xt_srow.assign(1, 0);
+      p->xt_srow.insert(p->xt_srow.end(), p->split_rows.begin(), p->split_rows.end());
+      p->xt_srow.push_back(n_rows);
+      p->xt_src.assign(xt.rchunk.begin(), xt.rchunk.end());
+      p->xt_sco.assign(K + 1, 0);
+      for (size_t k = 0; k <= K; ++k)
+        p->xt_sco[k] = std::lower_bound(xt.cont.begin(), xt.cont.end(), static_cast<int32_t>(p->xt_src[k])) -
+                       xt.cont.begin();
     }
-    if (C > 0) {
-      LHPC_HIP_TRY(hipMalloc(&d_segoff.a, xt.segoff.size() * 4));
-      LHPC_HIP_TRY(hipMemcpy(d_segoff.a, xt.segoff.data(), xt.segoff.size() * 4, hipMemcpyHostToDevice));
-      LHPC_HIP_TRY(hipMalloc(&d_vbase.a, vbase.size() * 4));
-      LHPC_HIP_TRY(hipMemcpy(d_vbase.a, vbase.data(), vbase.size() * 4, hipMemcpyHostToDevice));
-      int sbits = 0;
-      while ((int64_t{1} << sbits) < S) ++sbits;
-      if (ip)
-        hipLaunchKernelGGL((k_xt_scatter<T, true>), dim3(static_cast<unsigned>(C)), dim3(64), 0, nullptr,
-                           static_cast<const int32_t *>(d_ce.a), static_cast<const int32_t *>(d_segoff.a),
-                           static_cast<const int32_t *>(d_vbase.a), col_idx, static_cast<const T *>(val), W,
-                           static_cast<int>(S), sbits, p->d_col16, nullptr, p->d_perm, static_cast<T *>(p->d_val));
-      else
-        hipLaunchKernelGGL((k_xt_scatter<T, false>), dim3(static_cast<unsigned>(C)), dim3(64), 0, nullptr,
-                           static_cast<const int32_t *>(d_ce.a), static_cast<const int32_t *>(d_segoff.a),
-                           static_cast<const int32_t *>(d_vbase.a), col_idx, static_cast<const T *>(val), W,
-                           static_cast<int>(S), sbits, p->d_col16, p->d_perm, nullptr, static_cast<T *>(p->d_val));
-      LHPC_HIP_TRY(hipGetLastError());
-    }
-    const int64_t np = static_cast<int64_t>(xt.pieces.size() / 3);
-    if (np > 0) {
-      hipLaunchKernelGGL(k_xt_permute_blocks, dim3(static_cast<unsigned>(np)), dim3(64), 0, nullptr, p->d_pieces,
-                         static_cast<int>(16 / tsz), p->d_col16);
-      LHPC_HIP_TRY(hipGetLastError());
-    }
-    LHPC_HIP_TRY(hipDeviceSynchronize());
-  } else {
-    xtile_permute_gather_blocks(xt, static_cast<int>(16 / tsz));
-    LHPC_TRY(up(reinterpret_cast<void **>(&p->d_col16), xt.col16.get(), static_cast<size_t>(xt.total) * 2));
+    return LHPC_OK;
   }
-  if (pre) {  // the reduce's phase-A tables in place of the segment table (seg = bt, seghi = base_ne)
-    std::vector<uint32_t> pbt;
-    std::vector<int32_t> pbne;
-    xtile_phase_tables(xt, pbt, pbne);
-    LHPC_TRY(up(reinterpret_cast<void **>(&p->d_seg), pbt.data(), pbt.size() * 4));
-    LHPC_TRY(up(reinterpret_cast<void **>(&p->d_seghi), pbne.data(), pbne.size() * 4));
-    p->xt_seg_n = static_cast<int64_t>(pbt.size());
-    p->xt_seghi_n = static_cast<int64_t>(pbne.size());
-  } else {
-    std::vector<uint32_t> seg;
-    std::vector<int32_t> seghi;
-    xtile_segment_table(xt, seg, seghi);
-    LHPC_TRY(up(reinterpret_cast<void **>(&p->d_seg), seg.data(), seg.size() * 4));
-    LHPC_TRY(up(reinterpret_cast<void **>(&p->d_seghi), seghi.data(), seghi.size() * 4));
-    p->xt_seg_n = static_cast<int64_t>(seg.size());
-    p->xt_seghi_n = static_cast<int64_t>(seghi.size());
+};
+
+template <typename T>
+int build_t(lhpc_spmv_plan *p, RowPtrView rp, const int32_t *col_idx, const void *val, bool dev) {
+  XtileShape sh;
+  sh.n_rows = p->n_rows;
+  sh.n_cols = p->n_cols;
+  sh.nnz = p->nnz;
+  sh.elem_bytes = static_cast<int>(sizeof(T));
+  sh.M = XtBuild<T>::M;
+  sh.n_user_splits = static_cast<int>(p->split_rows.size());
+  sh.dev_build = dev;
+  hipDeviceProp_t prop;
+  if (hipGetDeviceProperties(&prop, p->device) == hipSuccess) sh.cus = prop.multiProcessorCount;
+  const char *tw = tuning_env("LHPC_XTILE_TW");  // tuning build only
+  sh.W = xtile_tile_width(sh.n_cols, sizeof(T), sh.cus, tw ? std::atoi(tw) != 0 : -1);
+  const int64_t tiles = (sh.n_cols + sh.W - 1) / sh.W;
+  sh.G = xtile_g<T>(static_cast<int>(std::min<int64_t>(tiles, kXtMaxTiles)));
+  const XtilePolicy pol = xtile_policy(sh, p->opt);
+  p->xt_p = pol.iperm ? 3 : 1;
+  p->xt_al = pol.aligned ? 1 : 0;
+  // a row-range plan (user splits) whose xg exceeds the cache gets per-range
+  // gather pieces for its own ranges (stage still gathers them all)
+  if (!p->split_rows.empty() && pol.ranges > 1) p->xt_mall = static_cast<int>(p->split_rows.size()) + 1;
+  if (pol.own_cuts) {
+    std::vector<int64_t> cuts(static_cast<size_t>(pol.ranges) + 1);
+    LHPC_TRY(lhpc_csr_partition_rows(rp.p, rp.bits, p->n_rows, pol.ranges, cuts.data()));
+    for (int k = 1; k < pol.ranges; ++k)
+      if (cuts[k] > 0 && cuts[k] < p->n_rows && (p->split_rows.empty() || cuts[k] > p->split_rows.back()))
+        p->split_rows.push_back(cuts[k]);
+    p->xt_mall = static_cast<int>(p->split_rows.size()) + 1;
   }
-  if (dev) {
-    // built above
-  } else if (ip) {
-    LHPC_TRY(up(reinterpret_cast<void **>(&p->d_perm), ipt.get(), nrun * 2));
-  } else {
-    // one sentinel entry past the stream: the reduce loads it for positions
-    // past m, and its perm is the spare LDS slot M
-    LHPC_TRY(up(reinterpret_cast<void **>(&p->d_perm), nullptr, static_cast<size_t>(xt.total + 2) * 2));
-    if (xt.total) LHPC_HIP_TRY(hipMemcpy(p->d_perm, xt.perm.get(), static_cast<size_t>(xt.total) * 2, hipMemcpyHostToDevice));
-    const uint16_t spare[2] = {static_cast<uint16_t>(M), static_cast<uint16_t>(M)};
-    LHPC_HIP_TRY(hipMemcpy(p->d_perm + xt.total, spare, 4, hipMemcpyHostToDevice));
-  }
-  LHPC_TRY(up(&p->d_xg, nullptr, static_cast<size_t>((p->xt_ring ? xt.ring_len : xt.total) + 2) * tsz));
-  LHPC_TRY(up(reinterpret_cast<void **>(&p->d_carry), nullptr, static_cast<size_t>(2 * C + 2) * 8));
-  LHPC_HIP_TRY(hipMemset(p->d_carry, 0, static_cast<size_t>(2 * C + 2) * 8));
-  if (!p->split_rows.empty()) {
-    const size_t K = p->split_rows.size() + 1;
-    p->xt_srow.assign(1, 0);
-    p->xt_srow.insert(p->xt_srow.end(), p->split_rows.begin(), p->split_rows.end());
-    p->xt_srow.push_back(n_rows);
-    p->xt_src.assign(xt.rchunk.begin(), xt.rchunk.end());
-    p->xt_sco.assign(K + 1, 0);
-    for (size_t k = 0; k <= K; ++k)
-      p->xt_sco[k] = std::lower_bound(xt.cont.begin(), xt.cont.end(), static_cast<int32_t>(p->xt_src[k])) -
-                     xt.cont.begin();
-  }
-  return LHPC_OK;
+  if (!pol.supported) return LHPC_ERR_UNSUPPORTED;
+  XtBuild<T> b{p, pol, rp};
+  LHPC_TRY(dev ? b.layout_device(col_idx, val) : b.layout_host(col_idx, val));
+  return b.upload();
 }
 
 }  // namespace
 
+// f<T>(…) for the plan's value type
+#define XT_TYPED(p, f, ...) ((p)->dtype == LHPC_F32 ? f<float>(__VA_ARGS__) : f<double>(__VA_ARGS__))
+
 template <typename T>
-int launch_mall(const lhpc_spmv_plan *p, const void *x, T *y, hipStream_t s) {
+int launch_t(const lhpc_spmv_plan *p, const void *x, void *yv, hipStream_t s) {
+  T *y = static_cast<T *>(yv);
+  if (p->xt_mall <= 1) {
+    LHPC_TRY(launch_gather<T>(p, x, s));
+    return launch_reduce<T>(p, 0, p->xt_C, 0, p->xt_cont, y, s);
+  }
   for (int k = 0; k < p->xt_mall; ++k) {
     LHPC_TRY(launch_gather<T>(p, x, s, p->xt_rpc[k], p->xt_rpc[k + 1]));
     LHPC_TRY(launch_reduce<T>(p, p->xt_src[k], p->xt_src[k + 1], 0, 0, y, s, p->xt_ring ? k : -1));
@@ -1356,15 +1284,7 @@ int launch_mall(const lhpc_spmv_plan *p, const void *x, T *y, hipStream_t s) {
 
 int xtile_launch(const lhpc_spmv_plan *p, const void *x, void *y, hipStream_t s) {
   if (p->n_rows == 0) return LHPC_OK;
-  if (p->xt_mall > 1)
-    return p->dtype == LHPC_F32 ? launch_mall<float>(p, x, static_cast<float *>(y), s)
-                                : launch_mall<double>(p, x, static_cast<double *>(y), s);
-  if (p->dtype == LHPC_F32) {
-    LHPC_TRY(launch_gather<float>(p, x, s));
-    return launch_reduce<float>(p, 0, p->xt_C, 0, p->xt_cont, static_cast<float *>(y), s);
-  }
-  LHPC_TRY(launch_gather<double>(p, x, s));
-  return launch_reduce<double>(p, 0, p->xt_C, 0, p->xt_cont, static_cast<double *>(y), s);
+  return XT_TYPED(p, launch_t, p, x, y, s);
 }
 
 // lhpc_spmv_stage: the gather of a split plan; lhpc_spmv_range: range k's
@@ -1372,22 +1292,21 @@ int xtile_launch(const lhpc_spmv_plan *p, const void *x, void *y, hipStream_t s)
 // range k's gather alone (plans with per-range pieces; ranges gathered in
 // order 0, 1, … — a range's first ≤ 7 entries come from the one before).
 int xtile_stage(const lhpc_spmv_plan *p, const void *x, hipStream_t s) {
-  return p->dtype == LHPC_F32 ? launch_gather<float>(p, x, s) : launch_gather<double>(p, x, s);
+  return XT_TYPED(p, launch_gather, p, x, s);
 }
 
 int xtile_range_gather(const lhpc_spmv_plan *p, const void *x, int k, hipStream_t s) {
   if (p->xt_rpc.empty() || k < 0 || k + 2 > static_cast<int>(p->xt_rpc.size())) return LHPC_ERR_UNSUPPORTED;
-  return p->dtype == LHPC_F32 ? launch_gather<float>(p, x, s, p->xt_rpc[k], p->xt_rpc[k + 1])
-                              : launch_gather<double>(p, x, s, p->xt_rpc[k], p->xt_rpc[k + 1]);
+  return XT_TYPED(p, launch_gather, p, x, s, p->xt_rpc[k], p->xt_rpc[k + 1]);
 }
 
-int xtile_range(const lhpc_spmv_plan *p, int k, void *yk, hipStream_t s) {
+template <typename T>
+int range_t(const lhpc_spmv_plan *p, int k, void *yk, hipStream_t s) {
   const int64_t c0 = p->xt_src[k], c1 = p->xt_src[k + 1], n0 = p->xt_sco[k], n1 = p->xt_sco[k + 1];
   const int ring = p->xt_ring ? k : -1;  // a ring plan: range k was the last one gathered
-  if (p->dtype == LHPC_F32)
-    return launch_reduce<float>(p, c0, c1, n0, n1, static_cast<float *>(yk) - p->xt_srow[k], s, ring);
-  return launch_reduce<double>(p, c0, c1, n0, n1, static_cast<double *>(yk) - p->xt_srow[k], s, ring);
+  return launch_reduce<T>(p, c0, c1, n0, n1, static_cast<T *>(yk) - p->xt_srow[k], s, ring);
 }
+int xtile_range(const lhpc_spmv_plan *p, int k, void *yk, hipStream_t s) { return XT_TYPED(p, range_t, p, k, yk, s); }
 
 int xtile_part_of_tile(int64_t tile, int64_t tile_width, int64_t n_cols, const int64_t *col_end, int n_parts) {
   const int64_t last = std::min((tile + 1) * tile_width, n_cols);  // exclusive end of the tile's columns
@@ -1425,8 +1344,7 @@ int xtile_column_parts(lhpc_spmv_plan *p, const int64_t *col_end, int n_parts) {
 
 int xtile_stage_part(const lhpc_spmv_plan *p, const void *x, int j, hipStream_t s) {
   if (p->xt_cpf.empty() || j < 0 || j + 2 > static_cast<int>(p->xt_cpf.size())) return LHPC_ERR_INVALID_ARG;
-  return p->dtype == LHPC_F32 ? launch_gather<float>(p, x, s, p->xt_cpf[j], p->xt_cpf[j + 1], p->d_pieces_cp)
-                              : launch_gather<double>(p, x, s, p->xt_cpf[j], p->xt_cpf[j + 1], p->d_pieces_cp);
+  return XT_TYPED(p, launch_gather, p, x, s, p->xt_cpf[j], p->xt_cpf[j + 1], p->d_pieces_cp);
 }
 
 int xtile_build(lhpc_spmv_plan *p, RowPtrView rp, const int32_t *col_idx, const void *val, size_t tsz) {

@@ -213,6 +213,201 @@ void check_xtile(const Csr &a, bool iperm, const std::vector<int64_t> &splits, i
   lhpc::xtile_permute_gather_blocks(xt, 4);
 }
 
+// The XTILE plan-build decisions (lhpc_plan.hpp xtile_tile_width,
+// xtile_policy, xtile_partition_policy) at full-size shapes, cus = 256.
+// Expected values are those of the plan build before these functions existed:
+//   W, tiles, ranges of C2 / C3 / the n = 80M column block are what info()
+//   reported for plans built on the GPU then (slice_width, slices, launches =
+//   2 per range and part: C2 39063 / 256 / 6, C3 20480 / 489 / 12, n = 80M
+//   three column blocks of 40960 / 652 / 2 each);
+//   everything else (iperm, aligned, ring, pre, nt, pieces, and every row
+//   without such a plan) is HAND-DERIVED from that build's code.
+// G (the reduce's segment-table entries per thread, the kernel file's
+// xtile_g) is an input: 1 up to 512 fp32 / 1024 fp64 tiles (fp32 ≈ 476–512:
+// 2), then ⌈tiles / 512⌉ resp. ⌈tiles / 1024⌉ rounded up to a power of two.
+struct PolicyCase {
+  const char *name;
+  int64_t n_rows, n_cols, nnz;
+  int elem_bytes, n_user_splits, G;
+  bool dev;
+  void (*set)(lhpc_options &);
+  // expected
+  int64_t W, tiles, min_piece, piece;
+  bool iperm, aligned, supported;
+  int cut, ranges;
+  bool own_cuts, pre;
+  int steps;
+  int K;  // the final range count the three below are asked at
+  bool ring, nt;
+  int64_t range_piece;
+};
+
+void check_xtile_policy() {
+  constexpr int64_t C2N = 10000000, C2Z = 150000000, MB256 = int64_t{256} << 20;
+  const PolicyCase cases[] = {
+      // full sizes, default options
+      {"C2", C2N, C2N, C2Z, 4, 0, 1, true, nullptr,
+       39063, 256, 104168, 292969, true, false, true, 256, 3, true, false, 8, 3, true, false, 244141},
+      {"C3", C2N, C2N, C2Z, 8, 0, 1, true, nullptr,
+       20480, 489, 65536, 292969, true, false, true, 256, 6, true, true, 8, 6, true, false, 122071},
+      {"n80m whole", 80000000, 80000000, 1200000000, 4, 0, 4, true, nullptr,
+       39063, 2048, 104168, 2343751, false, false, true, 256, 0, false, false, 8, 0, false, true, 0},
+      {"n80m column block", 80000000, 26666624, 400000000, 4, 0, 2, true, nullptr,
+       40960, 652, 109226, 781251, true, false, true, 256, 0, false, false, 8, 0, false, true, 0},
+      {"n150m whole", 150000000, 150000000, 2250000000, 4, 0, 8, true, nullptr,
+       39063, 3840, 104168, 4394532, false, false, true, 256, 0, false, false, 8, 0, false, true, 0},
+      // a rank's rows of C2 at two ranks, user splits: ranges only on request of the ring (fp64)
+      {"rank f32", 5000000, C2N, 75000000, 4, 3, 1, false, nullptr,
+       39063, 256, 104168, 146485, true, false, true, 256, 2, false, false, 8, 4, false, false, 104168},
+      {"rank f32 ring 2", 5000000, C2N, 75000000, 4, 3, 1, false, [](lhpc_options &o) { o.xtile_ring = 2; },
+       39063, 256, 104168, 146485, true, false, true, 256, 2, false, false, 8, 4, true, false, 104168},
+      {"rank f64", 5000000, C2N, 75000000, 8, 3, 1, false, nullptr,
+       20480, 489, 65536, 146485, true, false, true, 256, 0, false, true, 8, 0, false, true, 0},
+      {"rank f64 ring 2", 5000000, C2N, 75000000, 8, 3, 1, false, [](lhpc_options &o) { o.xtile_ring = 2; },
+       20480, 489, 65536, 146485, true, false, true, 256, 3, false, true, 8, 4, true, false, 91553},
+      // one option each, on C2 (C3 where the default differs there)
+      {"reduce perm", C2N, C2N, C2Z, 4, 0, 1, true, [](lhpc_options &o) { o.xtile_reduce = LHPC_XTILE_REDUCE_PERM; },
+       39063, 256, 104168, 292969, false, false, true, 256, 3, true, false, 8, 3, false, false, 244141},
+      {"align units", C2N, C2N, C2Z, 4, 0, 1, false, [](lhpc_options &o) { o.xtile_align = LHPC_XTILE_ALIGN_UNITS; },
+       39063, 256, 104168, 292969, true, true, true, 256, 3, true, false, 8, 3, false, false, 244141},
+      {"align units, device", C2N, C2N, C2Z, 4, 0, 1, true,
+       [](lhpc_options &o) { o.xtile_align = LHPC_XTILE_ALIGN_UNITS; },
+       39063, 256, 104168, 292969, true, true, false, 256, 3, true, false, 8, 3, false, false, 244141},
+      {"align units, G 8", 150000000, 150000000, 400000000, 4, 0, 8, false,
+       [](lhpc_options &o) { o.xtile_align = LHPC_XTILE_ALIGN_UNITS; },
+       39063, 3840, 104168, 781251, true, false, true, 256, 0, false, false, 8, 0, false, true, 0},
+      {"ranges 5", C2N, C2N, C2Z, 4, 0, 1, true, [](lhpc_options &o) { o.xtile_ranges = 5; },
+       39063, 256, 104168, 292969, true, false, true, 256, 5, true, false, 8, 5, true, false, 146484},
+      {"ring 1", C2N, C2N, C2Z, 4, 0, 1, true, [](lhpc_options &o) { o.xtile_ring = 1; },
+       39063, 256, 104168, 292969, true, false, true, 256, 3, true, false, 8, 3, false, false, 244141},
+      {"ring 1, C3", C2N, C2N, C2Z, 8, 0, 1, true, [](lhpc_options &o) { o.xtile_ring = 1; },
+       20480, 489, 65536, 292969, true, false, true, 256, 0, false, true, 8, 0, false, true, 0},
+      {"pretable 2", C2N, C2N, C2Z, 4, 0, 1, true, [](lhpc_options &o) { o.xtile_pretable = 2; },
+       39063, 256, 104168, 292969, true, false, true, 256, 3, true, true, 8, 3, true, false, 244141},
+      {"pretable 1, C3", C2N, C2N, C2Z, 8, 0, 1, true, [](lhpc_options &o) { o.xtile_pretable = 1; },
+       20480, 489, 65536, 292969, true, false, true, 256, 6, true, false, 8, 6, true, false, 122071},
+      {"pretable 2, G 2", 80000000, 26666624, 400000000, 4, 0, 2, true, [](lhpc_options &o) { o.xtile_pretable = 2; },
+       40960, 652, 109226, 781251, true, false, true, 256, 0, false, false, 8, 0, false, true, 0},
+      {"store nt", C2N, C2N, C2Z, 4, 0, 1, true, [](lhpc_options &o) { o.xtile_store = LHPC_STORE_NT; },
+       39063, 256, 104168, 292969, true, false, true, 256, 3, true, false, 8, 3, true, true, 244141},
+      {"store plain", 80000000, 26666624, 400000000, 4, 0, 2, true, [](lhpc_options &o) { o.xtile_store = LHPC_STORE_PLAIN; },
+       40960, 652, 109226, 781251, true, false, true, 256, 0, false, false, 8, 0, false, false, 0},
+      {"steps 3", C2N, C2N, C2Z, 4, 0, 1, true, [](lhpc_options &o) { o.xtile_steps = 3; },
+       39063, 256, 104168, 292969, true, false, true, 256, 3, true, false, 4, 3, true, false, 244141},
+      {"steps 16", C2N, C2N, C2Z, 4, 0, 1, true, [](lhpc_options &o) { o.xtile_steps = 16; },
+       39063, 256, 104168, 292969, true, false, true, 256, 3, true, false, 16, 3, true, false, 244141},
+      {"cut 64", C2N, C2N, C2Z, 4, 0, 1, true, [](lhpc_options &o) { o.xtile_cut = 64; },
+       39063, 256, 104168, 292969, true, false, true, 64, 3, true, false, 8, 3, true, false, 244141},
+      {"cut past M", C2N, C2N, C2Z, 4, 0, 1, true, [](lhpc_options &o) { o.xtile_cut = 100000; },
+       39063, 256, 104168, 292969, true, false, true, 8192, 3, true, false, 8, 3, true, false, 244141},
+      {"piece 1000", C2N, C2N, C2Z, 4, 0, 1, true, [](lhpc_options &o) { o.xtile_piece = 1000; },
+       39063, 256, 104168, 1000, true, false, true, 256, 3, true, false, 8, 3, true, false, 244141},
+      {"range piece 200", C2N, C2N, C2Z, 4, 0, 1, true, [](lhpc_options &o) { o.xtile_range_piece = 200; },
+       39063, 256, 104168, 292969, true, false, true, 256, 3, true, false, 8, 3, true, false, 200},
+      // xg at the 256 MB Infinity Cache and one entry past it (25 tiles)
+      {"xg = 256 MB", 1000000, 1000000, MB256 / 4, 4, 0, 1, true, nullptr,
+       40960, 25, 109226, 131073, true, false, true, 256, 0, false, false, 8, 0, false, false, 0},
+      {"xg > 256 MB", 1000000, 1000000, MB256 / 4 + 1, 4, 0, 1, true, nullptr,
+       40960, 25, 109226, 131073, true, false, true, 256, 2, true, false, 8, 2, true, false, 163841},
+      {"xg > 256 MB, one range", 1000000, 1000000, MB256 / 4 + 1, 4, 0, 1, true,
+       [](lhpc_options &o) { o.xtile_ranges = 1; },
+       40960, 25, 109226, 131073, true, false, true, 256, 1, false, false, 8, 1, false, true, 0},
+      // eight 200-MB ranges, and one entry more (nine: one range)
+      {"k = 8", 1000000, 1000000, 419430400, 4, 0, 1, true, nullptr,
+       40960, 25, 109226, 819201, true, false, true, 256, 8, true, false, 8, 8, true, false, 256001},
+      {"k = 9", 1000000, 1000000, 419430401, 4, 0, 1, true, nullptr,
+       40960, 25, 109226, 819201, true, false, true, 256, 0, false, false, 8, 0, false, true, 0},
+      // too few nonzeros per (range, tile) for ranges: C2's nonzeros over 8 times the columns
+      {"wide x", C2N, 80000000, C2Z, 4, 0, 4, true, nullptr,
+       39063, 2048, 104168, 292969, true, false, true, 256, 0, false, false, 8, 0, false, true, 0},
+      // the iperm reduce's 32-bit xg offsets: (nnz + 8·25 + 2·8192)·4 B just below 2 GiB, and at it
+      {"iperm below 2 GiB", 1000000, 1000000, 536854327, 4, 0, 1, true, nullptr,
+       40960, 25, 109226, 1048544, true, false, true, 256, 0, false, false, 8, 0, false, true, 0},
+      {"iperm at 2 GiB", 1000000, 1000000, 536854328, 4, 0, 1, true, nullptr,
+       40960, 25, 109226, 1048544, false, false, true, 256, 0, false, false, 8, 0, false, true, 0},
+  };
+  for (const PolicyCase &c : cases) {
+    lhpc_options o{};  // as lhpc_options_init: every choice automatic
+    o.struct_size = sizeof(o);
+    if (c.set) c.set(o);
+    lhpc::XtileShape s;
+    s.n_rows = c.n_rows;
+    s.n_cols = c.n_cols;
+    s.nnz = c.nnz;
+    s.elem_bytes = c.elem_bytes;
+    s.M = 8192;
+    s.cus = 256;
+    s.n_user_splits = c.n_user_splits;
+    s.dev_build = c.dev;
+    s.W = lhpc::xtile_tile_width(c.n_cols, static_cast<size_t>(c.elem_bytes), 256);
+    s.G = c.G;
+    const lhpc::XtilePolicy p = lhpc::xtile_policy(s, o);
+    const bool ok = p.W == c.W && p.tiles == c.tiles && p.min_piece == c.min_piece && p.piece == c.piece &&
+                    p.iperm == c.iperm && p.aligned == c.aligned && p.supported == c.supported && p.cut == c.cut &&
+                    p.ranges == c.ranges && p.own_cuts == c.own_cuts && p.pre == c.pre && p.steps == c.steps &&
+                    p.ring(c.K) == c.ring && p.nt(c.K) == c.nt && (c.K <= 1 || p.range_piece(c.K) == c.range_piece);
+    if (!ok)
+      std::fprintf(stderr,
+                   "xtile_policy %s: W %lld tiles %lld min_piece %lld piece %lld iperm %d aligned %d supported %d "
+                   "cut %d ranges %d own_cuts %d pre %d steps %d ring %d nt %d range_piece %lld\n",
+                   c.name, (long long)p.W, (long long)p.tiles, (long long)p.min_piece, (long long)p.piece, p.iperm,
+                   p.aligned, p.supported, p.cut, p.ranges, p.own_cuts, p.pre, p.steps, p.ring(c.K), p.nt(c.K),
+                   (long long)(c.K > 1 ? p.range_piece(c.K) : 0));
+    CHECK(ok);
+  }
+  // the tile width alone: the 10% rule's last accepted and first rejected
+  // tile count (233 / 232 → 256), the 4096-tile cap (4097 → 4352 tiles is
+  // within 10%; on 304 CUs 4000 → 4256), fp64 never, and the override
+  CHECK(lhpc::xtile_tile_width(40960 * 233, 4, 256) == 37280);
+  CHECK(lhpc::xtile_tile_width(40960 * 232, 4, 256) == 40960);
+  CHECK(lhpc::xtile_tile_width(40960 * 3900, 4, 256) == 39000);
+  CHECK(lhpc::xtile_tile_width(int64_t{40960} * 4097, 4, 256) == 40960);
+  CHECK(lhpc::xtile_tile_width(40960 * 4000, 4, 304) == 40960);
+  CHECK(lhpc::xtile_tile_width(20480 * 245, 8, 256) == 20480);
+  CHECK(lhpc::xtile_tile_width(C2N, 4, 256, 0) == 40960);
+  CHECK(lhpc::xtile_tile_width(20480 * 245, 8, 256, 1) == 19600);
+
+  // xtile_partition_policy: {tiles, cap, column blocks, parts}; cap = 2^31 − 1
+  // − 8·(tiles + 256) − 2^16.  HAND-DERIVED but for n = 80M's three blocks.
+  struct PartCase {
+    const char *name;
+    int64_t n_rows, n_cols, nnz;
+    size_t elem_bytes;
+    int n_splits;
+    void (*set)(lhpc_options &);
+    int64_t tiles, cap;
+    int B;
+    bool parts;
+  };
+  const PartCase parts[] = {
+      {"C2", C2N, C2N, C2Z, 4, 0, nullptr, 245, 2147414103, 1, false},
+      {"C3", C2N, C2N, C2Z, 8, 0, nullptr, 489, 2147412151, 1, false},
+      {"n80m", 80000000, 80000000, 1200000000, 4, 0, nullptr, 1954, 2147400431, 3, true},
+      {"n150m", 150000000, 150000000, 2250000000, 4, 0, nullptr, 3663, 2147386759, 3, true},
+      {"n80m, user splits", 80000000, 80000000, 1200000000, 4, 3, nullptr, 1954, 2147400431, 1, false},
+      {"col blocks 2", C2N, C2N, C2Z, 4, 0, [](lhpc_options &o) { o.xtile_col_blocks = 2; }, 245, 2147414103, 2, true},
+      {"col blocks 2, user splits", C2N, C2N, C2Z, 4, 2, [](lhpc_options &o) { o.xtile_col_blocks = 2; }, 245,
+       2147414103, 1, false},
+      {"part nnz", C2N, C2N, C2Z, 4, 0, [](lhpc_options &o) { o.xtile_part_nnz = 50000000; }, 245, 50000000, 1, true},
+      {"part nnz, user splits", C2N, C2N, C2Z, 4, 1, [](lhpc_options &o) { o.xtile_part_nnz = 50000000; }, 245,
+       50000000, 1, false},
+      // short rows bound the blocks: 8200 tiles, 10 per row → 2 blocks of 4100 tiles > 4096: no parts
+      {"4100 tiles per block", 1000000, int64_t{40960} * 8200, 10000000, 4, 0, nullptr, 8200, 2147350463, 2, false},
+      {"2734 tiles per block", 1000000, int64_t{40960} * 8200, 15000000, 4, 0, nullptr, 8200, 2147350463, 3, true},
+  };
+  for (const PartCase &c : parts) {
+    lhpc_options o{};  // as lhpc_options_init: every choice automatic
+    o.struct_size = sizeof(o);
+    if (c.set) c.set(o);
+    const lhpc::XtilePartition r = lhpc::xtile_partition_policy(c.n_rows, c.n_cols, c.nnz, c.elem_bytes, c.n_splits, o);
+    const bool ok = r.tiles == c.tiles && r.cap == c.cap && r.col_blocks == c.B && r.parts == c.parts;
+    if (!ok)
+      std::fprintf(stderr, "xtile_partition_policy %s: tiles %lld cap %lld B %d parts %d\n", c.name,
+                   (long long)r.tiles, (long long)r.cap, r.col_blocks, r.parts);
+    CHECK(ok);
+  }
+}
+
 void check_bad_csr() {
   // every builder pass indexes host arrays by col / row_ptr, so validation
   // must reject these before any of them runs (lhpc_spmv_plan_create)
@@ -271,6 +466,7 @@ void check_io(const Csr &a) {
 
 int main() {
   check_bad_csr();
+  check_xtile_policy();
   const Csr u = uniform(20000, 30000, 15, 0x5EED0001);
   const Csr p = powerlaw(20000, 20000, 3000, 0x5EED0004);
   const Csr e = uniform(777, 100, 0, 7);  // all rows empty

@@ -22,6 +22,11 @@ Provenance of every fixture:
   gen_checksums.json  sha256 of generator outputs for the BASELINE configs,
                  so a generator change cannot silently change the workload.
 
+  xtile_layout_pinned.json  layout digests, plan info and sha256(y) of the
+                 XTILE plans of test_xtile_layout_pinned, as built on the GPU
+                 by the library before its plan build was split into stages;
+                 only `make_golden.py xtile_layout_pinned` rewrites it.
+
 Usage:  python tests/golden/make_golden.py
 """
 import hashlib
@@ -167,7 +172,24 @@ def sort_fixtures():
         print("wrote", name)
 
 
+def xtile_layout_pinned():
+    """The XTILE plans of tests/test_gpu_spmv.py::test_xtile_layout_pinned as
+    the library in the tree builds them (needs the GPU): layout digests, plan
+    info and sha256 of y per case and build.  Recorded before a change that
+    must leave the plan build as it is; the change then has to reproduce it."""
+    import torch
+    from tests import test_gpu_spmv as T
+    gpu = torch.device("cuda:0")
+    cases = {c[0]: T.xtile_pinned_observe(L, gpu, c[0]) for c in T.XTILE_PINNED}
+    with open(os.path.join(HERE, "xtile_layout_pinned.json"), "w") as f:
+        json.dump({"source": "tests/golden/make_golden.py xtile_layout_pinned", "cases": cases}, f, indent=1)
+    print("wrote xtile_layout_pinned.json", len(cases), "cases")
+
+
 if __name__ == "__main__":
+    if sys.argv[1:] == ["xtile_layout_pinned"]:  # the one fixture that needs a GPU, and only on request
+        xtile_layout_pinned()
+        sys.exit(0)
     sort_fixtures()
     spmv_fixtures()
     blur_fixtures()

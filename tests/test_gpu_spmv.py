@@ -685,7 +685,7 @@ def test_xtile_col_blocks(lhpc, gpu, dtype, blocks, xt_layout):
     """XTILE column blocks (lhpc_options.xtile_col_blocks): the plan cuts the
     columns into B blocks, one XTILE plan each over x's column range, run in
     turn, every block after the first adding into y — the path a matrix takes
-    when x spans many tiles (lhpc_spmv.hip xtile_col_blocks_for), here forced
+    when x spans many tiles (lhpc_plan.cpp xtile_partition_policy), here forced
     at small size.  Long rows cut by chunk ends (the fix-up adds under the
     accumulation), empty rows, short rows with no entry in some blocks.
     Dyadic: bit-exact; random: within the bound; with row parts on top; the
@@ -962,3 +962,100 @@ def test_xtile_phase_tables(lhpc, gpu, dtype, ranges, tiles):
             assert np.array_equal(ys[0], yr)
         else:
             S.assert_spmv_close(ys[0], yr, asum)
+
+
+# (name, fp bits, tiles, options, user splits): every decision of the XTILE
+# plan build flipped by at least one case
+_PIN_SPLITS = [55, 56, 9000, 30057, 30059]
+XTILE_PINNED = [
+    ("f32_t3", 32, 3, {}, None),
+    ("f32_t256", 32, 256, {}, None),
+    ("f32_t500_narrowed", 32, 500, {}, None),
+    ("f32_t600", 32, 600, {}, None),
+    ("f32_t3_perm", 32, 3, {"xtile_reduce": 1}, None),
+    ("f32_t600_perm", 32, 600, {"xtile_reduce": 1}, None),
+    ("f32_t3_iperm_ranges1", 32, 3, {"xtile_reduce": 2, "xtile_ranges": 1}, None),
+    ("f32_t3_ranges3", 32, 3, {"xtile_ranges": 3}, None),
+    ("f32_t256_ranges3", 32, 256, {"xtile_ranges": 3}, None),
+    ("f32_t3_ranges3_noring", 32, 3, {"xtile_ranges": 3, "xtile_ring": 1}, None),
+    ("f32_t3_ranges3_perm", 32, 3, {"xtile_ranges": 3, "xtile_reduce": 1}, None),
+    ("f32_t3_ranges3_range_piece", 32, 3, {"xtile_ranges": 3, "xtile_range_piece": 200}, None),
+    ("f32_t3_splits", 32, 3, {}, _PIN_SPLITS),
+    ("f32_t3_splits_ranges2", 32, 3, {"xtile_ranges": 2}, _PIN_SPLITS),
+    ("f32_t3_splits_ring2", 32, 3, {"xtile_ranges": 2, "xtile_ring": 2}, _PIN_SPLITS),
+    ("f32_t3_pretable2", 32, 3, {"xtile_pretable": 2}, None),
+    ("f32_t256_pretable2_ranges3", 32, 256, {"xtile_pretable": 2, "xtile_ranges": 3}, None),
+    ("f32_t3_align", 32, 3, {"xtile_align": 2}, None),
+    ("f32_t3_store_nt", 32, 3, {"xtile_store": 2}, None),
+    ("f32_t3_steps4", 32, 3, {"xtile_steps": 4}, None),
+    ("f32_t3_cut64", 32, 3, {"xtile_cut": 64}, None),
+    ("f32_t3_piece1000", 32, 3, {"xtile_piece": 1000}, None),
+    ("f32_t256_col_blocks2", 32, 256, {"xtile_col_blocks": 2}, None),
+    ("f32_t3_part_nnz", 32, 3, {"xtile_part_nnz": 200_000}, None),
+    ("f64_t3", 64, 3, {}, None),
+    ("f64_t256", 64, 256, {}, None),
+    ("f64_t1100", 64, 1100, {}, None),
+    ("f64_t3_perm", 64, 3, {"xtile_reduce": 1}, None),
+    ("f64_t3_ranges3", 64, 3, {"xtile_ranges": 3}, None),
+    ("f64_t256_pretable1", 64, 256, {"xtile_pretable": 1}, None),
+    ("f64_t3_splits_ring2", 64, 3, {"xtile_ranges": 2, "xtile_ring": 2}, _PIN_SPLITS),
+    ("f64_t3_align", 64, 3, {"xtile_align": 2}, None),
+]
+_PIN_INPUTS = {}
+
+
+def _xtile_pinned_inputs(bits, tiles):
+    """The matrix and the non-dyadic x of a pinned case, built once per (dtype, tiles)."""
+    if (bits, tiles) not in _PIN_INPUTS:
+        dtype = np.float32 if bits == 32 else np.float64
+        lengths = [20000] + [3] * 50 + [5000, 4096, 4095, 1, 0, 9000] + [15] * 30000 + [0, 0] + [30000]
+        n_cols = (40960 if bits == 32 else 20480) * tiles - 7  # the last tile is partial
+        rp, col, val = _csr_from_lengths(lengths, n_cols, 0xC700 + bits + tiles, dyadic=False)
+        x = np.random.default_rng(0xC7F0 + tiles).uniform(-1, 1, n_cols).astype(dtype)
+        _PIN_INPUTS[(bits, tiles)] = (rp, col, val.astype(dtype), x, n_cols)
+    return _PIN_INPUTS[(bits, tiles)]
+
+
+def xtile_pinned_observe(lhpc, gpu, name):
+    """{build: {digest, info, y_sha256}} of a pinned case: the host build
+    (xtile_host_build = 1) and, where the options allow it, the default
+    (device) build.  Also the recorder's source (tests/golden/make_golden.py)."""
+    import hashlib
+    import torch
+    _, bits, tiles, opts, splits = next(c for c in XTILE_PINNED if c[0] == name)
+    rp, col, val, x, n_cols = _xtile_pinned_inputs(bits, tiles)
+    xd = torch.from_numpy(x).to(gpu)
+    out = {}
+    for build in ("host",) if opts.get("xtile_align") == 2 else ("host", "device"):
+        o = dict(opts, xtile_host_build=1) if build == "host" else dict(opts)
+        with lhpc.SpMVPlan(rp, col, val, n_cols, flags=FAMILIES["xtile"], options=o, splits=splits) as plan:
+            y = plan(xd).cpu().numpy()
+            out[build] = {"digest": [f"{d:016x}" for d in plan.layout_digest()], "info": plan.info(),
+                          "y_sha256": hashlib.sha256(y.tobytes()).hexdigest()}
+    return out
+
+
+@pytest.mark.parametrize("name", [c[0] for c in XTILE_PINNED])
+def test_xtile_layout_pinned(lhpc, gpu, name):
+    """The XTILE plan build reproduces tests/golden/xtile_layout_pinned.json,
+    recorded by tests/golden/make_golden.py before the build was split into
+    policy, layout and upload stages: the layout digests of every device
+    array, the plan info, and the SHA-256 of y for one fixed non-dyadic x (the
+    digests cover neither the ring's piece extensions nor the range-piece
+    offsets; y does).  Small forced-XTILE matrices (a 20000- and a 30000-long
+    row crossing chunks, empty rows, rows of 4095 / 4096, 0.52M nonzeros, a
+    partial last tile) over the tile counts of every reduce form (fp32 3 /
+    256 / 500 — narrowed to 512 — / 600, fp64 3 / 256 / 1100), perm and iperm,
+    cache ranges with and without the xg ring, user splits with
+    xtile_ring = 2, phase-A tables on and off, aligned segments, NT stores,
+    gather steps, the cut window, piece sizes, column blocks and row parts,
+    each from the host and the device build."""
+    import json
+    with open(os.path.join(S.GOLDEN, "xtile_layout_pinned.json")) as f:
+        want = json.load(f)["cases"][name]
+    got = xtile_pinned_observe(lhpc, gpu, name)
+    assert got.keys() == want.keys()
+    for build in want:
+        assert got[build]["info"]["kernel"] == lhpc.KERNEL_XTILE
+        for key in ("digest", "info", "y_sha256"):
+            assert got[build][key] == want[build][key], (build, key)
