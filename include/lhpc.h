@@ -361,6 +361,65 @@ int lhpc_spmv_plan_destroy(lhpc_spmv_plan *plan);
 int lhpc_csr_partition_rows(const void *row_ptr, int row_ptr_bits,
                             int64_t n_rows, int parts, int64_t *cuts);
 
+/* ------------------------------------------------------------ CSR SpMM   */
+/*
+ * Y = A·X: A an n_rows × n_cols CSR matrix, X a row-major n_cols × k block
+ * of vectors, Y row-major n_rows × k — one matrix applied to k vectors at
+ * once (multiple right-hand sides, block CG / LOBPCG, feature aggregation
+ * A·H).  A is streamed once per panel of ≤ 32 columns instead of once per
+ * vector, and the gather of row c of X is k·sizeof(T) contiguous bytes.
+ * The reference has no counterpart (it has no SpMV either).
+ *
+ * The plan COPIES A into HBM as CSR — row_ptr in the caller's 32/64-bit
+ * width, col_idx, val — beside the ADAPTIVE block table (≤ 2048 nonzeros and
+ * ≤ 256 rows per block, or one long row).  A is not re-encoded and there is
+ * no kernel family to choose.
+ *   dtype, row_ptr, row_ptr_bits, col_idx, val   as lhpc_spmv_plan_create
+ *   device   HIP device ordinal; -1 = current device
+ *   flags    LHPC_PLAN_VALIDATE (implied: A is always checked,
+ *            LHPC_ERR_BAD_CSR) and LHPC_PLAN_DEVICE_INPUT (the arrays are on
+ *            the plan's device: validated there, copied device to device;
+ *            only row_ptr comes to the host, for the block table).  Any
+ *            LHPC_PLAN_FORCE_* or *_PARTIALS flag: LHPC_ERR_INVALID_ARG.
+ * Null pointers, bad dtype / row_ptr_bits and negative sizes are
+ * LHPC_ERR_INVALID_ARG before any device is touched; no gfx950 device is
+ * LHPC_ERR_NO_DEVICE.
+ */
+typedef struct lhpc_spmm_plan lhpc_spmm_plan;
+typedef struct lhpc_spmm_plan_info {
+  int dtype, device;
+  int64_t n_rows, n_cols, nnz;
+  int64_t n_blocks, n_long_rows;   /* the ADAPTIVE block table (csr_build_blocks) */
+  int64_t device_bytes;            /* HBM held by the plan                       */
+  int panel_max;                   /* widest column panel one launch covers      */
+} lhpc_spmm_plan_info;
+
+int lhpc_spmm_plan_create(lhpc_spmm_plan **out, int dtype, int64_t n_rows, int64_t n_cols,
+                          int64_t nnz, const void *row_ptr, int row_ptr_bits,
+                          const int32_t *col_idx, const void *val, int device /* -1: current */,
+                          unsigned flags);
+/*
+ * Y = A·X for k ≥ 1 columns.  Element (c, j) of X is X[c·ldx + j] and
+ * element (i, j) of Y is Y[i·ldy + j]; the leading dimensions are in
+ * elements, ldx ≥ k and ldy ≥ k (else LHPC_ERR_INVALID_ARG, as are k < 1 and
+ * null pointers).  Elements j ≥ k of a row of Y are never written, so X and
+ * Y may be column slices of wider row-major arrays.  Y must not overlap X.
+ * Every Y[i, j] is the fp64 sum of row i's products rounded once, added in
+ * an order that depends on row i's structure only: column j of the result
+ * is bit-identical for every k, ldx, ldy and position j, and from run to run.
+ * With buffers_on_device != 0, X and Y are HBM pointers and the call is
+ * kernel launches on `stream` only (k ≤ 32: one; else one for the full
+ * 32-column panels and one for the rest): no allocation, synchronisation or
+ * host copy, so it can be captured into a graph.  Otherwise they are host
+ * pointers: X and Y are staged through plan-owned HBM buffers that grow on
+ * demand (strided 2-D copies when ld ≠ k) and the stream is synchronised
+ * before return.  One plan is used by one host thread at a time.
+ */
+int lhpc_spmm(lhpc_spmm_plan *plan, int k, const void *X, int64_t ldx, void *Y, int64_t ldy,
+              int buffers_on_device, void *stream);
+int lhpc_spmm_plan_info_get(const lhpc_spmm_plan *plan, lhpc_spmm_plan_info *info);
+int lhpc_spmm_plan_destroy(lhpc_spmm_plan *plan);
+
 /* -------------------------------------------------------- stencils      */
 /*
  * 17-tap (2·nblur+1) box blur along x of a ghost-padded 2-D grid, the

@@ -25,7 +25,7 @@ from typing import Optional
 import numpy as np
 
 __all__ = [
-    "LhpcError", "lib", "F32", "F64", "device_count", "SpMVPlan",
+    "LhpcError", "lib", "F32", "F64", "device_count", "SpMVPlan", "SpMMPlan",
     "csr_partition_rows", "blur_x", "blur_y", "stencil7", "stencil7_planes",
     "gen_uniform_csr", "gen_powerlaw_csr", "gen_values", "padded_shape",
     "PLAN_VALIDATE", "PLAN_FORCE_ROWGROUP", "PLAN_FORCE_ADAPTIVE", "PLAN_FORCE_XSLICE", "PLAN_FAST_PARTIALS", "PLAN_EXACT_PARTIALS",
@@ -72,6 +72,7 @@ ABI_SYMBOLS = (
     "lhpc_spmv_multi", "lhpc_spmv_plan_multi_info", "lhpc_dist_spmv_begin", "lhpc_dist_spmv_end",
     "lhpc_dist_chain_parts", "lhpc_dist_allgather_f64", "lhpc_dist_cg_solve", "lhpc_dist_spmv_plan_info",
     "lhpc_spmv_plan_layout_digest", "lhpc_dist_rccl_calls",
+    "lhpc_spmm_plan_create", "lhpc_spmm", "lhpc_spmm_plan_info_get", "lhpc_spmm_plan_destroy",
 )
 
 if not os.path.exists(LIB_PATH):
@@ -172,6 +173,15 @@ class PlanInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class SpMMPlanInfo(C.Structure):
+    """include/lhpc.h lhpc_spmm_plan_info."""
+    _fields_ = [("dtype", _i), ("device", _i), ("n_rows", _i64), ("n_cols", _i64), ("nnz", _i64),
+                ("n_blocks", _i64), ("n_long_rows", _i64), ("device_bytes", _i64), ("panel_max", _i)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 def _sig(name, res, *args):
     fn = getattr(lib, name)
     fn.restype = res
@@ -198,6 +208,10 @@ _sig("lhpc_spmv_multi", _i, _p, _p, _p, _p)
 _sig("lhpc_spmv_plan_layout_digest", _i, _p, _p, _i, C.POINTER(_i))
 _sig("lhpc_spmv_plan_multi_info", _i, _p, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), _p, _p)
 _sig("lhpc_spmv_plan_destroy", _i, _p)
+_sig("lhpc_spmm_plan_create", _i, C.POINTER(_p), _i, _i64, _i64, _i64, _p, _i, _p, _p, _i, _u)
+_sig("lhpc_spmm", _i, _p, _i, _p, _i64, _p, _i64, _i, _p)
+_sig("lhpc_spmm_plan_info_get", _i, _p, C.POINTER(SpMMPlanInfo))
+_sig("lhpc_spmm_plan_destroy", _i, _p)
 _sig("lhpc_csr_partition_rows", _i, _p, _i, _i64, _i, _p)
 for _n in ("lhpc_blur_x_f32", "lhpc_blur_y_f32"):
     _sig(_n, _i, _p, _p, _i64, _i64, _i64, _i, _i, _p)
@@ -310,6 +324,41 @@ def _stream_ptr(stream) -> Optional[int]:
 
 
 # ------------------------------------------------------------ SpMV
+def _csr_arrays(row_ptr, col_idx, val):
+    """The CSR arrays of a plan constructor: host numpy arrays (row_ptr
+    int32/int64, col_idx int32, val float32/float64), or contiguous CUDA
+    torch tensors of those types (``device`` is then their device index, else
+    None).  ``keep`` holds the arrays the pointers refer to."""
+    from types import SimpleNamespace
+    if _is_torch(row_ptr) and row_ptr.is_cuda:
+        import torch
+        if row_ptr.dtype not in (torch.int32, torch.int64) or col_idx.dtype != torch.int32:
+            raise TypeError("device row_ptr int32/int64 and col_idx int32")
+        if val.dtype not in (torch.float32, torch.float64):
+            raise TypeError("val must be float32 or float64")
+        for t in (row_ptr, col_idx, val):
+            if not (t.is_cuda and t.is_contiguous()):
+                raise ValueError("device CSR arrays must be contiguous CUDA tensors")
+        f32, device = val.dtype == torch.float32, row_ptr.device.index
+        rp_ptr, rp_bits = row_ptr.data_ptr(), 64 if row_ptr.dtype == torch.int64 else 32
+        col_ptr, val_ptr = col_idx.data_ptr(), val.data_ptr()
+    else:
+        row_ptr = np.ascontiguousarray(row_ptr)
+        col_idx = np.ascontiguousarray(col_idx, dtype=np.int32)
+        val = np.ascontiguousarray(val)
+        if row_ptr.dtype not in (np.int32, np.int64):
+            raise TypeError("row_ptr must be int32 or int64")
+        if val.dtype not in (np.float32, np.float64):
+            raise TypeError("val must be float32 or float64")
+        f32, device = val.dtype == np.float32, None
+        rp_ptr, rp_bits = row_ptr.ctypes.data, 64 if row_ptr.dtype == np.int64 else 32
+        col_ptr, val_ptr = col_idx.ctypes.data, val.ctypes.data
+    return SimpleNamespace(dtype=F32 if f32 else F64, np_dtype=np.dtype(np.float32 if f32 else np.float64),
+                           rp_ptr=rp_ptr, rp_bits=rp_bits, col_ptr=col_ptr, val_ptr=val_ptr,
+                           n_rows=int(row_ptr.shape[0] - 1), nnz=int(col_idx.shape[0]), device=device,
+                           keep=(row_ptr, col_idx, val))
+
+
 class SpMVPlan:
     """RAII plan for y = A·x (mirrors sparse::SpMVPlan<T> in include/sparse/SpMV.hpp).
 
@@ -328,43 +377,19 @@ class SpMVPlan:
         ordinals for a single-process multi-device plan (a
         device may repeat: several shares of one GPU); ``plan(x, y)`` then
         takes x, y on devices[0] and ``plan.multi(xs, ys)`` full replicas."""
-        if _is_torch(row_ptr) and row_ptr.is_cuda:
+        a = _csr_arrays(row_ptr, col_idx, val)
+        if a.device is not None:
             # device-resident CSR (LHPC_PLAN_DEVICE_INPUT): validated and, for
             # XTILE, laid out on the GPU; the tensors must live on the plan's device
-            import torch
-            if row_ptr.dtype not in (torch.int32, torch.int64) or col_idx.dtype != torch.int32:
-                raise TypeError("device row_ptr int32/int64 and col_idx int32")
-            if val.dtype not in (torch.float32, torch.float64):
-                raise TypeError("val must be float32 or float64")
-            for t in (row_ptr, col_idx, val):
-                if not (t.is_cuda and t.is_contiguous()):
-                    raise ValueError("device CSR arrays must be contiguous CUDA tensors")
             flags |= PLAN_DEVICE_INPUT
-            self.dtype = F32 if val.dtype == torch.float32 else F64
-            self.np_dtype = np.dtype(np.float32 if self.dtype == F32 else np.float64)
             if device is None and devices is None:
-                device = row_ptr.device.index
-            self._dev_arrays = (row_ptr, col_idx, val)
-            rp_ptr, rp_bits = row_ptr.data_ptr(), 64 if row_ptr.dtype == torch.int64 else 32
-            col_ptr, val_ptr = col_idx.data_ptr(), val.data_ptr()
-        else:
-            row_ptr = np.ascontiguousarray(row_ptr)
-            col_idx = np.ascontiguousarray(col_idx, dtype=np.int32)
-            val = np.ascontiguousarray(val)
-            if row_ptr.dtype not in (np.int32, np.int64):
-                raise TypeError("row_ptr must be int32 or int64")
-            if val.dtype == np.float32:
-                self.dtype = F32
-            elif val.dtype == np.float64:
-                self.dtype = F64
-            else:
-                raise TypeError("val must be float32 or float64")
-            self.np_dtype = val.dtype
-            rp_ptr, rp_bits = row_ptr.ctypes.data, 64 if row_ptr.dtype == np.int64 else 32
-            col_ptr, val_ptr = col_idx.ctypes.data, val.ctypes.data
-        self.n_rows = int(row_ptr.shape[0] - 1)
+                device = a.device
+            self._dev_arrays = a.keep
+        self.dtype, self.np_dtype = a.dtype, a.np_dtype
+        rp_ptr, rp_bits, col_ptr, val_ptr = a.rp_ptr, a.rp_bits, a.col_ptr, a.val_ptr
+        self.n_rows = a.n_rows
         self.n_cols = int(n_cols)
-        self.nnz = int(col_idx.shape[0])
+        self.nnz = a.nnz
         self._h = _p()
         if devices is not None:
             devices = [int(d) for d in devices]
@@ -473,6 +498,117 @@ class SpMVPlan:
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
             lib.lhpc_spmv_plan_destroy(self._h)
+            self._h = _p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+# ------------------------------------------------------------ SpMM
+def _block2d(a, np_dtype, k=None, writable=False):
+    """(pointer, on_device, rows, cols, leading dimension in elements) of a
+    row-major 2-D block: a numpy array or torch tensor with unit inner stride.
+    The row stride may exceed the width (a column slice of a wider array)."""
+    if _is_torch(a):
+        import torch
+        if a.dim() != 2:
+            raise ValueError("expected a 2-D block")
+        if a.dtype != (torch.float32 if np_dtype == np.float32 else torch.float64):
+            raise TypeError(f"expected dtype {np_dtype}, got {a.dtype}")
+        rows, cols = int(a.shape[0]), int(a.shape[1])
+        s0, s1 = (int(a.stride(0)), int(a.stride(1))) if rows and cols else (cols, 1)
+        ptr, dev = a.data_ptr(), bool(a.is_cuda)
+    elif isinstance(a, np.ndarray):
+        if a.ndim != 2:
+            raise ValueError("expected a 2-D block")
+        if a.dtype != np_dtype:
+            raise TypeError(f"expected dtype {np_dtype}, got {a.dtype}")
+        if writable and not a.flags.writeable:
+            raise ValueError("output array must be writable")
+        rows, cols = int(a.shape[0]), int(a.shape[1])
+        if rows and cols and (a.strides[0] % a.itemsize or a.strides[1] % a.itemsize):
+            raise ValueError("strides must be whole elements")
+        s0, s1 = (a.strides[0] // a.itemsize, a.strides[1] // a.itemsize) if rows and cols else (cols, 1)
+        ptr, dev = a.ctypes.data, False
+    else:
+        raise TypeError(f"expected numpy array or torch tensor, got {type(a)}")
+    if k is not None and cols != k:
+        raise ValueError(f"expected {k} columns, got {cols}")
+    if cols > 1 and s1 != 1:
+        raise ValueError("block must be row-major with unit inner stride")
+    if rows <= 1:
+        s0 = max(s0, cols)  # the stride of a single row is arbitrary
+    if s0 < cols:
+        raise ValueError("row stride smaller than the row (overlapping or transposed rows)")
+    return ptr, dev, rows, cols, max(s0, 1)
+
+
+class SpMMPlan:
+    """RAII plan for Y = A·X, X a row-major block of k vectors (mirrors
+    sparse::SpMMPlan<T> in include/sparse/SpMM.hpp; C ABI lhpc_spmm_*).
+
+    ``row_ptr`` int32/int64 (n_rows+1), ``col_idx`` int32 (nnz), ``val``
+    float32/float64 (nnz): host numpy arrays, or CUDA torch tensors on the
+    plan's device (LHPC_PLAN_DEVICE_INPUT).  A is copied to HBM once, as CSR.
+    """
+
+    def __init__(self, row_ptr, col_idx, val, n_cols: int, flags: int = 0, device: Optional[int] = None):
+        a = _csr_arrays(row_ptr, col_idx, val)
+        if a.device is not None:
+            flags |= PLAN_DEVICE_INPUT
+            if device is None:
+                device = a.device
+        self.dtype, self.np_dtype = a.dtype, a.np_dtype
+        self.n_rows, self.n_cols, self.nnz = a.n_rows, int(n_cols), a.nnz
+        self._h = _p()
+        _check(lib.lhpc_spmm_plan_create(
+            C.byref(self._h), self.dtype, self.n_rows, self.n_cols, self.nnz, a.rp_ptr, a.rp_bits, a.col_ptr,
+            a.val_ptr, -1 if device is None else int(device), flags), "lhpc_spmm_plan_create")
+
+    def info(self) -> dict:
+        inf = SpMMPlanInfo()
+        _check(lib.lhpc_spmm_plan_info_get(self._h, C.byref(inf)), "lhpc_spmm_plan_info_get")
+        return inf.as_dict()
+
+    def __call__(self, X, Y=None, stream=None):
+        """Y = A·X.  ``X``: 2-D, at least n_cols rows, k columns, unit inner
+        stride; the row stride is ldx, so a column slice of a wider row-major
+        array is taken as it is (no copy).  numpy in → numpy out
+        (synchronous); torch CUDA tensors → asynchronous on ``stream``
+        (default: torch's current stream).  ``Y``: (n_rows, k), allocated when
+        None; columns ≥ k of a wider array it is a slice of are not written."""
+        xp, xd, xr, k, ldx = _block2d(X, self.np_dtype)
+        if k < 1:
+            raise ValueError("X needs at least one column")
+        if Y is None:
+            if _is_torch(X):
+                import torch
+                Y = torch.empty((self.n_rows, k), dtype=X.dtype, device=X.device)
+            else:
+                Y = np.empty((self.n_rows, k), dtype=self.np_dtype)
+        yp, yd, yr, _, ldy = _block2d(Y, self.np_dtype, k=k, writable=True)
+        if xr < self.n_cols or yr < self.n_rows:
+            raise ValueError("X/Y have too few rows for the plan")
+        if xd != yd:
+            raise ValueError("X and Y must both be host or both be device buffers")
+        if xd and stream is None:
+            import torch
+            stream = torch.cuda.current_stream(Y.device)
+        _check(lib.lhpc_spmm(self._h, k, xp, ldx, yp, ldy, int(xd), _stream_ptr(stream)), "lhpc_spmm")
+        return Y
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            lib.lhpc_spmm_plan_destroy(self._h)
             self._h = _p()
 
     def __del__(self):

@@ -1,0 +1,382 @@
+// lhpc_spmm.hip — Y = A·X for gfx950 (MI355X): A an n_rows × n_cols CSR
+// matrix kept as CSR in HBM, X a row-major n_cols × k block of vectors
+// (element (c, j) at X[c·ldx + j]), Y row-major n_rows × k (include/lhpc.h
+// "CSR SpMM").  The reference has no SpMV and no SpMM; the
+// operator is Y[i, j] = Σ_{m=row_ptr[i]}^{row_ptr[i+1]-1} val[m]·X[col_idx[m], j].
+//
+// k_spmm_csr<T, I, P>: one 256-thread workgroup per block of the ADAPTIVE
+// block table (csr_build_blocks: ≤ 2048 nonzeros and ≤ 256 rows, or one long
+// row) and per panel of P columns.  The workgroup streams its block's
+// col/val (and row bounds) once into LDS, coalesced and non-temporal; then
+// G = 256/P lane groups walk the rows, lane j of a group owning column
+// col0 + j: every lane of a group reads the same LDS entry (a broadcast) and
+// one gather instruction of a group touches P·sizeof(T) contiguous bytes of
+// row col_idx[m] of X — a whole 128-B line at P = 32 in fp32.
+// Numerics: fp64 accumulation in registers, one rounding at the store
+// (SURVEY §8c), and a summation order per element that depends on row i's
+// structure only — never on k, ldx, ldy, the panel or the lane:
+//   rows of ≤ 2048 nonzeros  ascending m;
+//   longer rows              kLongStreams = 64 interleaved streams (stream s
+//                            holds m ≡ s mod 64, each summed ascending), the
+//                            64 partials then added in ascending s.
+// No atomics, fixed order: results are identical run to run.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <new>
+#include <vector>
+
+#include "lhpc_plan.hpp"
+#include "lhpc_spmv_impl.hpp"
+
+struct lhpc_spmm_plan {
+  int dtype = LHPC_F32;
+  int device = 0;
+  int rp64 = 0;  // device row_ptr is int64 (the caller's width is kept)
+  int64_t n_rows = 0, n_cols = 0, nnz = 0;
+  void *d_row_ptr = nullptr;
+  int32_t *d_col = nullptr;
+  void *d_val = nullptr;
+  int64_t *d_blocks = nullptr;  // {first row, its row_ptr} per block boundary
+  int64_t n_blocks = 0, n_long = 0;
+  int64_t bytes = 0;
+  // host-buffer calls: packed (ld = k) copies of X and Y, grown on demand
+  void *d_xstage = nullptr, *d_ystage = nullptr;
+  size_t xstage_bytes = 0, ystage_bytes = 0;
+};
+
+namespace lhpc {
+namespace {
+
+constexpr int kSpmmBlockNnz = 2048;  // csr_build_blocks' nonzeros per block
+constexpr int kSpmmPanelMax = 32;    // widest column panel of one launch
+constexpr int kLongStreams = 64;     // long rows: interleaved partial sums (= 256 / the narrowest panel)
+// gathers in flight per lane before the dependent adds (8: DESIGN.md §4.2;
+// -DLHPC_SPMM_UNROLL=n builds the A/B variants, results are identical)
+#ifndef LHPC_SPMM_UNROLL
+#define LHPC_SPMM_UNROLL 8
+#endif
+constexpr int kSpmmUnroll = LHPC_SPMM_UNROLL;
+
+template <typename T, typename I, int P>
+__global__ __launch_bounds__(kBlock) void k_spmm_csr(
+    const I *__restrict__ row_ptr, const int32_t *__restrict__ col, const T *__restrict__ val,
+    const T *__restrict__ X, int64_t ldx, T *__restrict__ Y, int64_t ldy, const int64_t *__restrict__ blocks,
+    int64_t n_rows, int64_t n_cols, int k, int panel0) {
+  static_assert(P == 4 || P == 8 || P == 16 || P == 32, "panel widths");
+  constexpr int G = kBlock / P;        // lane groups per workgroup
+  constexpr int NS = kLongStreams / G;  // long rows: streams per group
+  static_assert(NS >= 1 && NS * G == kLongStreams, "every stream has one group");
+  // the block's stream (normal blocks) or the long row's partials: never both
+  constexpr size_t kStreamBytes = kSpmmBlockNnz * (sizeof(int32_t) + sizeof(T));
+  constexpr size_t kPartBytes = sizeof(double) * kLongStreams * P;
+  __shared__ __attribute__((aligned(16))) unsigned char smem[kStreamBytes > kPartBytes ? kStreamBytes : kPartBytes];
+  __shared__ int32_t lrp[kBlock + 1];  // row bounds relative to the block's first nonzero
+  T *lval = reinterpret_cast<T *>(smem);
+  int32_t *lcol = reinterpret_cast<int32_t *>(smem + kSpmmBlockNnz * sizeof(T));
+  double *part = reinterpret_cast<double *>(smem);
+
+  const int tid = threadIdx.x;
+  const int j = tid & (P - 1), g = tid / P;
+  const int64_t r0 = blocks[2 * blockIdx.x], base = blocks[2 * blockIdx.x + 1];
+  const int64_t r1 = blocks[2 * blockIdx.x + 2];
+  const int64_t cnt = blocks[2 * blockIdx.x + 3] - base;
+  const int nrows = static_cast<int>(r1 - r0);
+  const int cj = panel0 + static_cast<int>(blockIdx.y) * P + j;  // this lane's column of X and Y
+  const bool act = cj < k;
+  const T *__restrict__ xj = X + cj;
+  T *__restrict__ yj = Y + cj;
+
+  if (cnt > kSpmmBlockNnz) {
+    // one long row: the group of stream s adds nonzeros s, s + 64, … ascending
+    double a[NS];
+#pragma unroll
+    for (int u = 0; u < NS; ++u) a[u] = 0.0;
+    if (act) {
+      for (int64_t m0 = 0; m0 < cnt; m0 += kLongStreams) {
+        int32_t c[NS];
+        T v[NS], x[NS];
+#pragma unroll
+        for (int u = 0; u < NS; ++u) {
+          const int64_t m = m0 + g + u * G;
+          c[u] = -1;
+          v[u] = T(0);
+          if (m < cnt) {
+            c[u] = ld_stream(col + base + m);
+            v[u] = ld_stream(val + base + m);
+          }
+        }
+#pragma unroll
+        for (int u = 0; u < NS; ++u) {
+          x[u] = T(0);
+          if (c[u] >= 0) {
+            LHPC_DEVICE_CHECK(c[u] < n_cols);
+            x[u] = xj[static_cast<int64_t>(c[u]) * ldx];
+          }
+        }
+#pragma unroll
+        for (int u = 0; u < NS; ++u)
+          if (c[u] >= 0) a[u] += static_cast<double>(v[u]) * static_cast<double>(x[u]);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < NS; ++u) part[(g + u * G) * P + j] = a[u];
+    __syncthreads();
+    if (g == 0 && act) {
+      double t = part[j];
+      for (int s = 1; s < kLongStreams; ++s) t += part[s * P + j];
+      LHPC_DEVICE_CHECK(r0 < n_rows);
+      yj[r0 * ldy] = static_cast<T>(t);
+    }
+    return;
+  }
+
+  // stream phase: the block's col/val once, coalesced; row bounds with them
+  constexpr int PER = kSpmmBlockNnz / kBlock;
+  {
+    int32_t c[PER];
+    T v[PER];
+#pragma unroll
+    for (int i = 0; i < PER; ++i) {
+      const int64_t m = i * kBlock + tid;
+      c[i] = 0;
+      v[i] = T(0);
+      if (m < cnt) {
+        c[i] = ld_stream(col + base + m);
+        v[i] = ld_stream(val + base + m);
+      }
+    }
+    if (tid <= nrows) lrp[tid] = static_cast<int32_t>(static_cast<int64_t>(row_ptr[r0 + tid]) - base);
+    if (tid == 0 && nrows == kBlock) lrp[kBlock] = static_cast<int32_t>(cnt);
+#pragma unroll
+    for (int i = 0; i < PER; ++i) {
+      const int m = i * kBlock + tid;
+      if (m < cnt) {
+        lcol[m] = c[i];
+        lval[m] = v[i];
+      }
+    }
+  }
+  __syncthreads();
+  if (!act) return;
+
+  // product phase: group g takes rows g, g + G, …; per row the nonzeros in
+  // ascending order, kSpmmUnroll gathers issued before the dependent adds
+  for (int r = g; r < nrows; r += G) {
+    const int rs = lrp[r], re = lrp[r + 1];
+    double a = 0.0;
+    for (int m0 = rs; m0 < re; m0 += kSpmmUnroll) {
+      T v[kSpmmUnroll], x[kSpmmUnroll];
+#pragma unroll
+      for (int u = 0; u < kSpmmUnroll; ++u) {
+        v[u] = T(0);
+        x[u] = T(0);
+        if (m0 + u < re) {
+          const int32_t c = lcol[m0 + u];
+          v[u] = lval[m0 + u];
+          LHPC_DEVICE_CHECK(c >= 0 && c < n_cols);
+          x[u] = xj[static_cast<int64_t>(c) * ldx];
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < kSpmmUnroll; ++u)
+        if (m0 + u < re) a += static_cast<double>(v[u]) * static_cast<double>(x[u]);
+    }
+    LHPC_DEVICE_CHECK(r0 + r < n_rows);
+    yj[(r0 + r) * ldy] = static_cast<T>(a);
+  }
+}
+
+template <typename T, typename I, int P>
+int launch_panel(const lhpc_spmm_plan *p, int k, const void *X, int64_t ldx, void *Y, int64_t ldy, int panel0,
+                 int n_panels, hipStream_t s) {
+  hipLaunchKernelGGL((k_spmm_csr<T, I, P>), dim3(static_cast<unsigned>(p->n_blocks), static_cast<unsigned>(n_panels)),
+                     dim3(kBlock), 0, s, static_cast<const I *>(p->d_row_ptr), p->d_col,
+                     static_cast<const T *>(p->d_val), static_cast<const T *>(X), ldx, static_cast<T *>(Y), ldy,
+                     p->d_blocks, p->n_rows, p->n_cols, k, panel0);
+  return check_launch(s);
+}
+
+// full panels of kSpmmPanelMax columns in one launch (blockIdx.y = panel), then
+// the remaining columns in a launch of the narrowest panel that holds them
+template <typename T, typename I>
+int launch_spmm(const lhpc_spmm_plan *p, int k, const void *X, int64_t ldx, void *Y, int64_t ldy, hipStream_t s) {
+  const int full = k / kSpmmPanelMax, rest = k % kSpmmPanelMax;
+  if (full > 65535) return LHPC_ERR_UNSUPPORTED;  // gridDim.y
+  if (full > 0) LHPC_TRY((launch_panel<T, I, kSpmmPanelMax>(p, k, X, ldx, Y, ldy, 0, full, s)));
+  const int p0 = full * kSpmmPanelMax;
+  if (rest == 0) return LHPC_OK;
+  if (rest <= 4) return launch_panel<T, I, 4>(p, k, X, ldx, Y, ldy, p0, 1, s);
+  if (rest <= 8) return launch_panel<T, I, 8>(p, k, X, ldx, Y, ldy, p0, 1, s);
+  if (rest <= 16) return launch_panel<T, I, 16>(p, k, X, ldx, Y, ldy, p0, 1, s);
+  return launch_panel<T, I, 32>(p, k, X, ldx, Y, ldy, p0, 1, s);
+}
+
+int launch(const lhpc_spmm_plan *p, int k, const void *X, int64_t ldx, void *Y, int64_t ldy, hipStream_t s) {
+  if (p->n_blocks == 0) return LHPC_OK;
+  if (p->dtype == LHPC_F32)
+    return p->rp64 ? launch_spmm<float, int64_t>(p, k, X, ldx, Y, ldy, s)
+                   : launch_spmm<float, int32_t>(p, k, X, ldx, Y, ldy, s);
+  return p->rp64 ? launch_spmm<double, int64_t>(p, k, X, ldx, Y, ldy, s)
+                 : launch_spmm<double, int32_t>(p, k, X, ldx, Y, ldy, s);
+}
+
+// host ↔ device copy of an `rows` × k block with leading dimensions (elements)
+int copy_block(void *dst, int64_t ldd, const void *src, int64_t lds, int64_t rows, int k, size_t tsz,
+               hipMemcpyKind kind) {
+  if (rows == 0) return LHPC_OK;
+  if (ldd == k && lds == k) {
+    LHPC_HIP_TRY(hipMemcpy(dst, src, static_cast<size_t>(rows) * k * tsz, kind));
+  } else {
+    LHPC_HIP_TRY(hipMemcpy2D(dst, static_cast<size_t>(ldd) * tsz, src, static_cast<size_t>(lds) * tsz,
+                             static_cast<size_t>(k) * tsz, static_cast<size_t>(rows), kind));
+  }
+  return LHPC_OK;
+}
+
+int grow(void **buf, size_t &have, size_t want, int64_t &acct) {
+  if (want <= have && *buf) return LHPC_OK;
+  if (*buf) {
+    LHPC_HIP_TRY(hipFree(*buf));
+    *buf = nullptr;
+    acct -= static_cast<int64_t>(have);
+    have = 0;
+  }
+  LHPC_TRY(dmalloc(buf, want, acct));
+  have = std::max<size_t>(want, 16);
+  return LHPC_OK;
+}
+
+int plan_build(lhpc_spmm_plan *p, const void *row_ptr, int bits, const int32_t *col_idx, const void *val,
+               bool device_input) {
+  const size_t tsz = p->dtype == LHPC_F32 ? 4 : 8;
+  const size_t rpb = static_cast<size_t>(p->n_rows + 1) * (bits / 8);
+  const size_t nnz = static_cast<size_t>(p->nnz);
+  const hipMemcpyKind kind = device_input ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+  // row_ptr on the host, for the block table
+  std::vector<unsigned char> hrp;
+  const void *rp_host = row_ptr;
+  if (device_input) {
+    // the arrays may still be in flight on any stream of the caller
+    LHPC_HIP_TRY(hipDeviceSynchronize());
+    LHPC_TRY(validate_csr_device(row_ptr, bits, col_idx, p->n_rows, p->n_cols, p->nnz));
+    hrp.resize(rpb);
+    LHPC_HIP_TRY(hipMemcpy(hrp.data(), row_ptr, rpb, hipMemcpyDeviceToHost));
+    rp_host = hrp.data();
+  }
+  LHPC_TRY(dmalloc(&p->d_row_ptr, rpb, p->bytes));
+  LHPC_TRY(dmalloc(reinterpret_cast<void **>(&p->d_col), nnz * 4, p->bytes));
+  LHPC_TRY(dmalloc(&p->d_val, nnz * tsz, p->bytes));
+  LHPC_HIP_TRY(hipMemcpy(p->d_row_ptr, row_ptr, rpb, kind));
+  if (nnz) {
+    LHPC_HIP_TRY(hipMemcpy(p->d_col, col_idx, nnz * 4, kind));
+    LHPC_HIP_TRY(hipMemcpy(p->d_val, val, nnz * tsz, kind));
+  }
+  const RowPtrView rp{rp_host, bits};
+  const std::vector<int64_t> b = csr_build_blocks(rp, p->n_rows, p->n_long);
+  p->n_blocks = static_cast<int64_t>(b.size()) - 1;
+  if (p->n_blocks > INT32_MAX) return LHPC_ERR_UNSUPPORTED;  // gridDim.x
+  std::vector<int64_t> bp(2 * b.size());
+  for (size_t i = 0; i < b.size(); ++i) {
+    bp[2 * i] = b[i];
+    bp[2 * i + 1] = rp[b[i]];
+  }
+  LHPC_TRY(dmalloc(reinterpret_cast<void **>(&p->d_blocks), bp.size() * 8, p->bytes));
+  LHPC_HIP_TRY(hipMemcpy(p->d_blocks, bp.data(), bp.size() * 8, hipMemcpyHostToDevice));
+  return LHPC_OK;
+}
+
+}  // namespace
+}  // namespace lhpc
+
+using namespace lhpc;
+
+extern "C" int lhpc_spmm_plan_create(lhpc_spmm_plan **out, int dtype, int64_t n_rows, int64_t n_cols, int64_t nnz,
+                                     const void *row_ptr, int row_ptr_bits, const int32_t *col_idx, const void *val,
+                                     int device, unsigned flags) {
+  try {
+    if (!out) return LHPC_ERR_INVALID_ARG;
+    *out = nullptr;
+    if ((dtype != LHPC_F32 && dtype != LHPC_F64) || n_rows < 0 || n_cols < 0 || nnz < 0 || !row_ptr ||
+        (row_ptr_bits != 32 && row_ptr_bits != 64) || n_cols > INT32_MAX || (nnz > 0 && (!col_idx || !val)) ||
+        (row_ptr_bits == 32 && nnz > INT32_MAX) || device < -1)
+      return LHPC_ERR_INVALID_ARG;
+    // there is one kernel family and no partial sums to choose
+    if (flags & ~static_cast<unsigned>(LHPC_PLAN_VALIDATE | LHPC_PLAN_DEVICE_INPUT)) return LHPC_ERR_INVALID_ARG;
+    RocTxRange rx("lhpc_spmm_plan_create");
+    const bool device_input = (flags & LHPC_PLAN_DEVICE_INPUT) != 0;
+    // always (LHPC_PLAN_VALIDATE is implied): the kernel indexes X by col_idx
+    if (!device_input) LHPC_TRY(validate_csr(row_ptr, row_ptr_bits, col_idx, n_rows, n_cols, nnz));
+    int dev = device;
+    if (dev < 0 ? hipGetDevice(&dev) != hipSuccess : hipSetDevice(dev) != hipSuccess) {
+      (void)hipGetLastError();
+      return LHPC_ERR_NO_DEVICE;
+    }
+    if (!is_gfx950(dev)) return LHPC_ERR_NO_DEVICE;
+    auto *p = new (std::nothrow) lhpc_spmm_plan();
+    if (!p) return LHPC_ERR_ALLOC;
+    p->dtype = dtype;
+    p->device = dev;
+    p->rp64 = row_ptr_bits == 64;
+    p->n_rows = n_rows;
+    p->n_cols = n_cols;
+    p->nnz = nnz;
+    const int st = plan_build(p, row_ptr, row_ptr_bits, col_idx, val, device_input);
+    if (st != LHPC_OK) {
+      lhpc_spmm_plan_destroy(p);
+      return st;
+    }
+    *out = p;
+    return LHPC_OK;
+  } LHPC_ABI_CATCH
+}
+
+extern "C" int lhpc_spmm(lhpc_spmm_plan *p, int k, const void *X, int64_t ldx, void *Y, int64_t ldy, int on_device,
+                         void *stream) {
+  try {
+    // sizes first, the plan is read after them
+    if (!p || k < 1 || ldx < k || ldy < k) return LHPC_ERR_INVALID_ARG;
+    if ((p->n_cols > 0 && !X) || (p->n_rows > 0 && !Y)) return LHPC_ERR_INVALID_ARG;
+    RocTxRange rx("lhpc_spmm");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    LHPC_HIP_TRY(hipSetDevice(p->device));
+    if (on_device) return launch(p, k, X, ldx, Y, ldy, s);
+    // host buffers: synchronous strided copies through packed plan-owned
+    // buffers, which only host-buffer calls touch (they end synchronised)
+    const size_t tsz = p->dtype == LHPC_F32 ? 4 : 8;
+    LHPC_TRY(grow(&p->d_xstage, p->xstage_bytes, static_cast<size_t>(p->n_cols) * k * tsz, p->bytes));
+    LHPC_TRY(grow(&p->d_ystage, p->ystage_bytes, static_cast<size_t>(p->n_rows) * k * tsz, p->bytes));
+    LHPC_TRY(copy_block(p->d_xstage, k, X, ldx, p->n_cols, k, tsz, hipMemcpyHostToDevice));
+    LHPC_TRY(launch(p, k, p->d_xstage, k, p->d_ystage, k, s));
+    LHPC_HIP_TRY(hipStreamSynchronize(s));
+    return copy_block(Y, ldy, p->d_ystage, k, p->n_rows, k, tsz, hipMemcpyDeviceToHost);
+  } LHPC_ABI_CATCH
+}
+
+extern "C" int lhpc_spmm_plan_info_get(const lhpc_spmm_plan *p, lhpc_spmm_plan_info *info) {
+  try {
+    if (!p || !info) return LHPC_ERR_INVALID_ARG;
+    info->dtype = p->dtype;
+    info->device = p->device;
+    info->n_rows = p->n_rows;
+    info->n_cols = p->n_cols;
+    info->nnz = p->nnz;
+    info->n_blocks = p->n_blocks;
+    info->n_long_rows = p->n_long;
+    info->device_bytes = p->bytes;
+    info->panel_max = kSpmmPanelMax;
+    return LHPC_OK;
+  } LHPC_ABI_CATCH
+}
+
+extern "C" int lhpc_spmm_plan_destroy(lhpc_spmm_plan *p) {
+  try {
+    if (!p) return LHPC_OK;
+    (void)hipSetDevice(p->device);
+    for (void *q : {p->d_row_ptr, static_cast<void *>(p->d_col), p->d_val, static_cast<void *>(p->d_blocks),
+                    p->d_xstage, p->d_ystage})
+      if (q) (void)hipFree(q);
+    delete p;
+    return LHPC_OK;
+  } LHPC_ABI_CATCH
+}

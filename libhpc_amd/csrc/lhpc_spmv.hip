@@ -149,12 +149,6 @@ int colblock_device(const void *d_rp, int bits, const int32_t *d_col, const void
   return static_cast<int>(e);
 }
 
-bool is_gfx950(int dev) {
-  hipDeviceProp_t p;
-  if (hipGetDeviceProperties(&p, dev) != hipSuccess) return false;
-  return std::strncmp(p.gcnArchName, "gfx950", 6) == 0;
-}
-
 int launch(const lhpc_spmv_plan *p, const void *x, void *y, hipStream_t s) {
   if (!p->parts.empty()) {
     const size_t tsz = p->dtype == LHPC_F32 ? 4 : 8;
@@ -568,21 +562,7 @@ int plan_create_device_input(lhpc_spmv_plan **out, int dtype, int64_t n_rows, in
   // creation is synchronous anyway)
   LHPC_HIP_TRY(hipDeviceSynchronize());
   const size_t tsz = dtype == LHPC_F32 ? 4 : 8;
-  {
-    unsigned *flag = nullptr;
-    LHPC_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&flag), 4));
-    hipError_t e = hipMemset(flag, 0, 4);
-    if (e == hipSuccess) {
-      hipLaunchKernelGGL(k_validate_device_csr, dim3(1024), dim3(256), 0, nullptr, row_ptr, row_ptr_bits, col_idx,
-                         n_rows, n_cols, nnz, flag);
-      e = hipGetLastError();
-    }
-    unsigned bad = 0;
-    if (e == hipSuccess) e = hipMemcpy(&bad, flag, 4, hipMemcpyDeviceToHost);
-    (void)hipFree(flag);
-    if (e != hipSuccess) return static_cast<int>(e);
-    if (bad) return LHPC_ERR_BAD_CSR;
-  }
+  LHPC_TRY(validate_csr_device(row_ptr, row_ptr_bits, col_idx, n_rows, n_cols, nnz));
   const size_t rpb = static_cast<size_t>(n_rows + 1) * (row_ptr_bits / 8);
   std::vector<unsigned char> hrp(rpb);
   LHPC_HIP_TRY(hipMemcpy(hrp.data(), row_ptr, rpb, hipMemcpyDeviceToHost));
@@ -673,6 +653,30 @@ int plan_create_device_input(lhpc_spmv_plan **out, int dtype, int64_t n_rows, in
 }
 
 }  // namespace
+
+bool is_gfx950(int dev) {
+  hipDeviceProp_t p;
+  if (hipGetDeviceProperties(&p, dev) != hipSuccess) return false;
+  return std::strncmp(p.gcnArchName, "gfx950", 6) == 0;
+}
+
+int validate_csr_device(const void *row_ptr, int row_ptr_bits, const int32_t *col_idx, int64_t n_rows,
+                        int64_t n_cols, int64_t nnz) {
+  unsigned *flag = nullptr;
+  LHPC_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&flag), 4));
+  hipError_t e = hipMemset(flag, 0, 4);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(k_validate_device_csr, dim3(1024), dim3(256), 0, nullptr, row_ptr, row_ptr_bits, col_idx,
+                       n_rows, n_cols, nnz, flag);
+    e = hipGetLastError();
+  }
+  unsigned bad = 0;
+  if (e == hipSuccess) e = hipMemcpy(&bad, flag, 4, hipMemcpyDeviceToHost);
+  (void)hipFree(flag);
+  if (e != hipSuccess) return static_cast<int>(e);
+  return bad ? LHPC_ERR_BAD_CSR : LHPC_OK;
+}
+
 }  // namespace lhpc
 
 using namespace lhpc;

@@ -4,6 +4,8 @@
 //   lhpc_spmv_csr.hip     ROWGROUP / ADAPTIVE (CSR kept as is), SELL (short rows)
 //   lhpc_spmv_xslice.hip  XSLICE (XCD-local column slices + partial reduce)
 //   lhpc_spmv_xtile.hip   XTILE (x tiles in LDS: tile gather + chunk reduce)
+//   lhpc_spmm.hip         Y = A·X (its own plan type; shares the ADAPTIVE
+//                         block table and the device validation declared here)
 // The reference has no SpMV: the operator is
 // y[i] = Σ_{k=row_ptr[i]}^{row_ptr[i+1]-1} val[k]·x[col_idx[k]].
 #pragma once
@@ -177,6 +179,14 @@ void multi_free(lhpc_spmv_plan *p);
 int multi_home(lhpc_spmv_plan *p, const void *x, void *y, int on_device, hipStream_t s);
 void local_csr_from_global(LocalCsr &out, RowPtrView rp, const int32_t *col_idx, const void *val, size_t tsz,
                            const int64_t *cuts, int nranks, int K, int rank);
+
+// ---- lhpc_spmv.hip (shared with lhpc_spmm.hip)
+bool is_gfx950(int dev);
+// validate_csr on the GPU for LHPC_PLAN_DEVICE_INPUT (row_ptr / col_idx in HBM
+// of the current device): LHPC_ERR_BAD_CSR when row_ptr[0] != 0, row_ptr
+// decreases, row_ptr[n_rows] != nnz or a column is outside [0, n_cols)
+int validate_csr_device(const void *row_ptr, int row_ptr_bits, const int32_t *col_idx, int64_t n_rows,
+                        int64_t n_cols, int64_t nnz);
 
 // ---- lhpc_spmv_csr.hip
 int csr_launch(const lhpc_spmv_plan *p, const void *x, void *y, hipStream_t s);
