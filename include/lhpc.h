@@ -417,6 +417,33 @@ int lhpc_spmm_plan_create(lhpc_spmm_plan **out, int dtype, int64_t n_rows, int64
  */
 int lhpc_spmm(lhpc_spmm_plan *plan, int k, const void *X, int64_t ldx, void *Y, int64_t ldy,
               int buffers_on_device, void *stream);
+/*
+ * lhpc_spmm with per-column dots in its epilogue — the k-column counterpart
+ * of lhpc_spmv_dot, the p·Ap of lhpc_cg_solve_multi.  Y = A·X exactly as
+ * lhpc_spmm stores it (bit-identical), and dots[j] = Σ_i W[i, j]·Y[i, j] over
+ * the n_rows rows, formed in fp64 from the stored (rounded) Y.  Device
+ * buffers only; asynchronous on `stream`.  W is n_rows × k with leading
+ * dimension ldw ≥ k and may be X when A is square (Y must overlap neither X
+ * nor W); dots is k doubles in HBM.
+ * k < 1, a leading dimension below k and null X, Y, W or dots are
+ * LHPC_ERR_INVALID_ARG before the plan is read.
+ * Summation order of dots[j] — a function of A's block table and n_rows only,
+ * never of k, ldx, ldy, ldw, the panel or the column's position, so dots[j]
+ * is bit-identical however column j is presented, and from run to run: per
+ * block of the table 64 interleaved streams (stream s = the block's local
+ * rows r ≡ s mod 64, added in ascending r), the 64 stream sums added in
+ * ascending s (a long-row block contributes its one product); then the block
+ * partials per column, thread t of one 256-thread workgroup adding blocks
+ * t, t + 256, … ascending, the 64 lanes of each wave by an xor butterfly
+ * (offsets 32 … 1) and the 4 wave sums in ascending order.  A matrix without
+ * blocks (no rows or no nonzeros) gives dots = 0.
+ * The block partials live in a plan-owned n_blocks × k fp64 buffer (counted
+ * in device_bytes) that grows when k exceeds every earlier call's: such a
+ * call allocates (and synchronises the device); every other call is kernel
+ * launches only.
+ */
+int lhpc_spmm_dot(lhpc_spmm_plan *plan, int k, const void *X, int64_t ldx, void *Y, int64_t ldy,
+                  const void *W, int64_t ldw, double *dots, void *stream);
 int lhpc_spmm_plan_info_get(const lhpc_spmm_plan *plan, lhpc_spmm_plan_info *info);
 int lhpc_spmm_plan_destroy(lhpc_spmm_plan *plan);
 
@@ -580,6 +607,47 @@ int lhpc_cg_solve(lhpc_spmv_plan *plan, const void *b, void *x, double tol,
                   double *resid_out, void *stream);
 int lhpc_vec_dot(int dtype, int64_t n, const void *a, const void *b,
                  double *out, void *stream);
+/*
+ * Conjugate gradient for k right-hand sides on an SpMM plan: k independent CG
+ * recurrences kept in step, so that one lhpc_spmm_dot per iteration serves
+ * all of them (A is streamed once per 32 columns instead of once per
+ * column).  This is not block CG: column j goes through exactly the
+ * operations of a one-column solve of B_j.
+ * B and X are row-major n × k HBM blocks of the plan's dtype with leading
+ * dimensions ldb, ldx ≥ k (elements).  X holds the initial guesses on entry
+ * and the solutions on return, updated in place; elements j ≥ k of a row of
+ * X, and B, are never written.  B must not overlap X.  The matrix must be
+ * square (else LHPC_ERR_INVALID_ARG, as are k < 1, ldb < k, ldx < k,
+ * max_iter < 0, a tol that is not ≥ 0 and null B or X — all before the plan
+ * is read).  Synchronous.
+ * Per column, with element arithmetic in the plan's dtype, α and β fp64
+ * quotients cast to it, fp64 dots:
+ *   bb = B_j·B_j; R = B − A·X; P = R; rr = R_j·R_j; stop = tol²·(bb > 0 ? bb : 1)
+ *   rr ≤ stop: done at 0 iterations.  Then for it = 1 … max_iter, while any
+ *   column is active:
+ *     Q = A·P, pq = P_j·Q_j; α = rr/pq; R_j −= α·Q_j; rr' = R_j·R_j
+ *     at it % check_every == 0 or it == max_iter (the only host
+ *     synchronisations): rr' not finite → the column broke down: frozen,
+ *     X_j not updated; rr' ≤ stop → X_j += α·P_j, frozen, done at `it`
+ *     else β = rr'/rr; X_j += α·P_j; P_j = R_j + β·P_j
+ * Nothing of a frozen column is written again.  iters_out[j] (host, k ints,
+ * may be NULL) is the iteration at which column j stopped, resid_out[j]
+ * (host, k doubles, may be NULL) its sqrt(max(rr, 0)) / sqrt(bb > 0 ? bb : 1).
+ * If a column broke down, the others are still solved to the end, its
+ * residual is reported non-finite and the call returns LHPC_ERR_INTERNAL.
+ * The rr dots are summed in an order that depends on n only (tiles of 256
+ * rows, in each 64 interleaved streams of rows r ≡ s mod 64 added in
+ * ascending s, the tiles per column as lhpc_spmm_dot adds its blocks), so
+ * X_j, iters_out[j] and resid_out[j] are bit-identical for every k, ldb, ldx
+ * and position j, and from run to run.
+ * The work — R, P, Q packed at ld = k, per-column scalars and dot partials,
+ * a pinned host buffer — belongs to the plan, grows with k, is counted in
+ * device_bytes and freed with the plan.  One solve per plan at a time: a
+ * second concurrent one returns LHPC_ERR_BUSY.
+ */
+int lhpc_cg_solve_multi(lhpc_spmm_plan *plan, int k, const void *B, int64_t ldb, void *X,
+                        int64_t ldx, double tol, int max_iter, int check_every,
+                        int *iters_out, double *resid_out, void *stream);
 int lhpc_cg_step_xr(int dtype, int64_t n, const double *alpha_num,
                     const double *alpha_den, void *x, const void *p, void *r,
                     const void *q, double *rr_out, void *stream);

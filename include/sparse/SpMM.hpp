@@ -7,6 +7,11 @@
 //                             the arrays' padded row lengths are the leading
 //                             dimensions, ghost cells are skipped and untouched
 //   sparse::spmm(plan, k, d_X, ldx, d_Y, ldy, stream)  raw HBM pointers (async)
+//   sparse::spmm_dot(plan, k, d_X, ldx, d_Y, ldy, d_W, ldw, d_dots, stream)
+//                             the same with d_dots[j] = Σ_i W[i,j]·Y[i,j] (async)
+//   sparse::cg(plan, k, d_B, ldb, d_X, ldx, tol, max_iter, check_every, stream)
+//                             k CG solves in step on one SpMM per iteration
+//                             (synchronous) → CGMultiResult
 // Forwards to the C ABI (include/lhpc.h "CSR SpMM"); non-zero status →
 // std::system_error (include/lhpc_error.hpp).  The reference has no SpMM (and
 // no SpMV); the operator and its numerics are defined in DESIGN.md.
@@ -17,6 +22,7 @@
 #include <cstdint>
 #include <type_traits>
 #include <utility>
+#include <vector>
 
 #include "../hpc/HPCHighDimensionFlatArray.hpp"
 #include "../lhpc.h"
@@ -101,6 +107,35 @@ template <typename T>
 void spmm(SpMMPlan<T> &plan, int k, const T *d_X, std::int64_t ldx, T *d_Y, std::int64_t ldy,
           void *stream = nullptr) {
   lhpc::checkLhpc(lhpc_spmm(plan.native(), k, d_X, ldx, d_Y, ldy, 1, stream));
+}
+
+// Y = A·X as spmm stores it and d_dots[j] = Σ_i W[i, j]·Y[i, j] (fp64, k
+// doubles in HBM) in one pass over A; W is n_rows × k and may be X when A is
+// square.  Asynchronous on `stream`.
+template <typename T>
+void spmm_dot(SpMMPlan<T> &plan, int k, const T *d_X, std::int64_t ldx, T *d_Y, std::int64_t ldy, const T *d_W,
+              std::int64_t ldw, double *d_dots, void *stream = nullptr) {
+  lhpc::checkLhpc(lhpc_spmm_dot(plan.native(), k, d_X, ldx, d_Y, ldy, d_W, ldw, d_dots, stream));
+}
+
+// per column: the iteration at which it stopped and its ‖r‖/‖b‖
+struct CGMultiResult {
+  std::vector<int> iterations;
+  std::vector<double> residual;
+};
+
+// Conjugate gradient for the k columns of d_B (row-major n × k in HBM) on one
+// SpMM per iteration; d_X holds the initial guesses and receives the
+// solutions (lhpc_cg_solve_multi).  Synchronous.  A column that broke down
+// (the matrix is not SPD) makes the call throw, like every non-zero status.
+template <typename T>
+CGMultiResult cg(SpMMPlan<T> &plan, int k, const T *d_B, std::int64_t ldb, T *d_X, std::int64_t ldx,
+                 double tol = 1e-8, int max_iter = 1000, int check_every = 1, void *stream = nullptr) {
+  if (k < 1) lhpc::throwLhpcError(LHPC_ERR_INVALID_ARG, __FILE__, __LINE__);
+  CGMultiResult r{std::vector<int>(static_cast<std::size_t>(k)), std::vector<double>(static_cast<std::size_t>(k))};
+  lhpc::checkLhpc(lhpc_cg_solve_multi(plan.native(), k, d_B, ldb, d_X, ldx, tol, max_iter, check_every,
+                                      r.iterations.data(), r.residual.data(), stream));
+  return r;
 }
 
 }  // namespace sparse

@@ -25,7 +25,7 @@ from typing import Optional
 import numpy as np
 
 __all__ = [
-    "LhpcError", "lib", "F32", "F64", "device_count", "SpMVPlan", "SpMMPlan",
+    "LhpcError", "lib", "F32", "F64", "device_count", "SpMVPlan", "SpMMPlan", "spmm_dot", "cg_multi",
     "csr_partition_rows", "blur_x", "blur_y", "stencil7", "stencil7_planes",
     "gen_uniform_csr", "gen_powerlaw_csr", "gen_values", "padded_shape",
     "PLAN_VALIDATE", "PLAN_FORCE_ROWGROUP", "PLAN_FORCE_ADAPTIVE", "PLAN_FORCE_XSLICE", "PLAN_FAST_PARTIALS", "PLAN_EXACT_PARTIALS",
@@ -73,6 +73,7 @@ ABI_SYMBOLS = (
     "lhpc_dist_chain_parts", "lhpc_dist_allgather_f64", "lhpc_dist_cg_solve", "lhpc_dist_spmv_plan_info",
     "lhpc_spmv_plan_layout_digest", "lhpc_dist_rccl_calls",
     "lhpc_spmm_plan_create", "lhpc_spmm", "lhpc_spmm_plan_info_get", "lhpc_spmm_plan_destroy",
+    "lhpc_spmm_dot", "lhpc_cg_solve_multi",
 )
 
 if not os.path.exists(LIB_PATH):
@@ -210,6 +211,8 @@ _sig("lhpc_spmv_plan_multi_info", _i, _p, C.POINTER(_i), C.POINTER(_i), C.POINTE
 _sig("lhpc_spmv_plan_destroy", _i, _p)
 _sig("lhpc_spmm_plan_create", _i, C.POINTER(_p), _i, _i64, _i64, _i64, _p, _i, _p, _p, _i, _u)
 _sig("lhpc_spmm", _i, _p, _i, _p, _i64, _p, _i64, _i, _p)
+_sig("lhpc_spmm_dot", _i, _p, _i, _p, _i64, _p, _i64, _p, _i64, _p, _p)
+_sig("lhpc_cg_solve_multi", _i, _p, _i, _p, _i64, _p, _i64, C.c_double, _i, _i, _p, _p, _p)
 _sig("lhpc_spmm_plan_info_get", _i, _p, C.POINTER(SpMMPlanInfo))
 _sig("lhpc_spmm_plan_destroy", _i, _p)
 _sig("lhpc_csr_partition_rows", _i, _p, _i, _i64, _i, _p)
@@ -622,6 +625,76 @@ class SpMMPlan:
 
     def __exit__(self, *exc):
         self.close()
+
+
+def spmm_dot(plan: "SpMMPlan", X, W, Y=None, out=None, stream=None):
+    """Y = A·X as ``plan(X)`` stores it, and out[j] = Σ_i W[i, j]·Y[i, j] in
+    fp64, in one pass over A (lhpc_spmm_dot).  ``X`` (≥ n_cols rows) and ``W``
+    (≥ n_rows rows) are CUDA tensors of k columns with unit inner stride —
+    column slices of wider tensors are taken as they are; ``W`` may be ``X``
+    when A is square.  ``Y`` (n_rows × k) and ``out`` (k float64) are
+    allocated when None.  Asynchronous on ``stream`` (default: torch's
+    current stream).  Returns (Y, out)."""
+    import torch
+    xp, xd, xr, k, ldx = _block2d(X, plan.np_dtype)
+    if k < 1:
+        raise ValueError("X needs at least one column")
+    wp, wd, wr, _, ldw = _block2d(W, plan.np_dtype, k=k)
+    if not (xd and wd):
+        raise ValueError("spmm_dot: X and W must be device tensors")
+    if Y is None:
+        Y = torch.empty((plan.n_rows, k), dtype=X.dtype, device=X.device)
+    yp, yd, yr, _, ldy = _block2d(Y, plan.np_dtype, k=k, writable=True)
+    if not yd:
+        raise ValueError("spmm_dot: Y must be a device tensor")
+    if out is None:
+        out = torch.empty(k, dtype=torch.float64, device=X.device)
+    if not (_is_torch(out) and out.is_cuda and out.dtype == torch.float64 and out.is_contiguous()
+            and out.numel() >= k):
+        raise ValueError("out must be a contiguous float64 device tensor of k elements")
+    if xr < plan.n_cols or yr < plan.n_rows or wr < plan.n_rows:
+        raise ValueError("X/Y/W have too few rows for the plan")
+    if stream is None:
+        stream = torch.cuda.current_stream(Y.device)
+    _check(lib.lhpc_spmm_dot(plan._h, k, xp, ldx, yp, ldy, wp, ldw, out.data_ptr(), _stream_ptr(stream)),
+           "lhpc_spmm_dot")
+    return Y, out
+
+
+def cg_multi(plan: "SpMMPlan", B, X=None, tol: float = 1e-8, max_iter: int = 1000, check_every: int = 1,
+             stream=None):
+    """Solve A·X = B (A SPD, the plan's matrix) for the k columns of ``B`` by
+    k conjugate-gradient recurrences kept in step (lhpc_cg_solve_multi): one
+    SpMM per iteration serves every column.  ``B`` and ``X`` (the initial
+    guesses, default 0, updated in place) are CUDA tensors of k columns with
+    unit inner stride; column slices of wider tensors are taken as they are.
+    Returns (X, iters, resid): int32 and float64 numpy arrays of length k.  A
+    non-zero status raises LhpcError carrying ``.iters`` and ``.resid`` (a
+    column that broke down has a non-finite residual; the others are solved)."""
+    import torch
+    bp, bd, br, k, ldb = _block2d(B, plan.np_dtype)
+    if k < 1:
+        raise ValueError("B needs at least one column")
+    if X is None:
+        if not bd:
+            raise ValueError("cg_multi: B and X must be device tensors")
+        X = torch.zeros((plan.n_rows, k), dtype=B.dtype, device=B.device)
+    xp, xd, xr, _, ldx = _block2d(X, plan.np_dtype, k=k, writable=True)
+    if not (bd and xd):
+        raise ValueError("cg_multi: B and X must be device tensors")
+    if br < plan.n_rows or xr < plan.n_rows:
+        raise ValueError("B/X have too few rows for the plan")
+    if stream is None:
+        stream = torch.cuda.current_stream(X.device)
+    iters = np.zeros(k, dtype=np.int32)
+    resid = np.zeros(k, dtype=np.float64)
+    st = lib.lhpc_cg_solve_multi(plan._h, k, bp, ldb, xp, ldx, tol, max_iter, check_every, iters.ctypes.data,
+                                 resid.ctypes.data, _stream_ptr(stream))
+    if st != 0:
+        err = LhpcError(st, "lhpc_cg_solve_multi")
+        err.iters, err.resid = iters, resid
+        raise err
+    return X, iters, resid
 
 
 def csr_partition_rows(row_ptr: np.ndarray, parts: int) -> np.ndarray:

@@ -20,6 +20,25 @@
 //                            holds m ≡ s mod 64, each summed ascending), the
 //                            64 partials then added in ascending s.
 // No atomics, fixed order: results are identical run to run.
+//
+// k_spmm_dot<T, I, P>: the same phases, in a kernel of its own (sharing one
+// body moved k_spmm_csr's fp64 instantiations past their 64 VGPRs), with
+// dots[j] = Σ_i W[i, j]·Y[i, j] in the epilogue (lhpc_spmm_dot; the p·Ap of the
+// multi-RHS CG), from the stored (rounded) Y in fp64; the stored Y is
+// bit-identical to k_spmm_csr's.  Order
+// per column, a function of A's block table and n_rows only (never of k, the
+// leading dimensions, the panel or the column's position):
+//   per block    64 interleaved streams, stream s = the block's local rows
+//                r ≡ s (mod 64) added in ascending r (group g owns streams
+//                g, g + G, …: row g + t·G goes to accumulator t mod 64/G);
+//                the 64 stream sums added in ascending s.  A long-row block
+//                contributes its one product.
+//   per column   the block partials (plan-owned n_blocks × k fp64) added by
+//                k_coldot_finish, one workgroup per column: thread t adds
+//                blocks t, t + 256, … ascending, then the fixed tree of
+//                block_sum — a function of n_blocks only.
+// Lanes past k skip the product phase but stay until the barrier that
+// precedes the reuse of LDS for the stream sums.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -27,29 +46,14 @@
 #include <vector>
 
 #include "lhpc_plan.hpp"
+#include "lhpc_spmm_plan.hpp"
 #include "lhpc_spmv_impl.hpp"
-
-struct lhpc_spmm_plan {
-  int dtype = LHPC_F32;
-  int device = 0;
-  int rp64 = 0;  // device row_ptr is int64 (the caller's width is kept)
-  int64_t n_rows = 0, n_cols = 0, nnz = 0;
-  void *d_row_ptr = nullptr;
-  int32_t *d_col = nullptr;
-  void *d_val = nullptr;
-  int64_t *d_blocks = nullptr;  // {first row, its row_ptr} per block boundary
-  int64_t n_blocks = 0, n_long = 0;
-  int64_t bytes = 0;
-  // host-buffer calls: packed (ld = k) copies of X and Y, grown on demand
-  void *d_xstage = nullptr, *d_ystage = nullptr;
-  size_t xstage_bytes = 0, ystage_bytes = 0;
-};
 
 namespace lhpc {
 namespace {
 
+static_assert(kPanelThreads == kBlock, "the panel kernels are kBlock wide");
 constexpr int kSpmmBlockNnz = 2048;  // csr_build_blocks' nonzeros per block
-constexpr int kSpmmPanelMax = 32;    // widest column panel of one launch
 constexpr int kLongStreams = 64;     // long rows: interleaved partial sums (= 256 / the narrowest panel)
 // gathers in flight per lane before the dependent adds (8: DESIGN.md §4.2;
 // -DLHPC_SPMM_UNROLL=n builds the A/B variants, results are identical)
@@ -57,6 +61,32 @@ constexpr int kLongStreams = 64;     // long rows: interleaved partial sums (= 2
 #define LHPC_SPMM_UNROLL 8
 #endif
 constexpr int kSpmmUnroll = LHPC_SPMM_UNROLL;
+
+// one row of the block in LDS times column xj of X: the nonzeros in ascending
+// order, kSpmmUnroll gathers issued before the dependent adds; rounded once
+template <typename T>
+__device__ __forceinline__ T spmm_row(const T *lval, const int32_t *lcol, int rs, int re, const T *__restrict__ xj,
+                                      int64_t ldx, int64_t n_cols) {
+  double a = 0.0;
+  for (int m0 = rs; m0 < re; m0 += kSpmmUnroll) {
+    T v[kSpmmUnroll], x[kSpmmUnroll];
+#pragma unroll
+    for (int u = 0; u < kSpmmUnroll; ++u) {
+      v[u] = T(0);
+      x[u] = T(0);
+      if (m0 + u < re) {
+        const int32_t c = lcol[m0 + u];
+        v[u] = lval[m0 + u];
+        LHPC_DEVICE_CHECK(c >= 0 && c < n_cols);
+        x[u] = xj[static_cast<int64_t>(c) * ldx];
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < kSpmmUnroll; ++u)
+      if (m0 + u < re) a += static_cast<double>(v[u]) * static_cast<double>(x[u]);
+  }
+  return static_cast<T>(a);
+}
 
 template <typename T, typename I, int P>
 __global__ __launch_bounds__(kBlock) void k_spmm_csr(
@@ -187,38 +217,191 @@ __global__ __launch_bounds__(kBlock) void k_spmm_csr(
   }
 }
 
+// k_spmm_csr with the per-column dot in its epilogue (header comment): the
+// same stream and product phases — Y is stored bit-identical — as a kernel of
+// its own, so that k_spmm_csr's code and register budget stay what they were.
+template <typename T, typename I, int P>
+__global__ __launch_bounds__(kBlock) void k_spmm_dot(
+    const I *__restrict__ row_ptr, const int32_t *__restrict__ col, const T *__restrict__ val,
+    const T *__restrict__ X, int64_t ldx, T *__restrict__ Y, int64_t ldy, const int64_t *__restrict__ blocks,
+    int64_t n_rows, int64_t n_cols, int k, int panel0, const T *W, int64_t ldw, double *__restrict__ dpart) {
+  static_assert(P == 4 || P == 8 || P == 16 || P == 32, "panel widths");
+  constexpr int G = kBlock / P;        // lane groups per workgroup
+  constexpr int NS = kLongStreams / G;  // long rows: streams per group
+  static_assert(NS >= 1 && NS * G == kLongStreams, "every stream has one group");
+  // the block's stream (normal blocks) or the long row's partials: never both
+  constexpr size_t kStreamBytes = kSpmmBlockNnz * (sizeof(int32_t) + sizeof(T));
+  constexpr size_t kPartBytes = sizeof(double) * kLongStreams * P;
+  __shared__ __attribute__((aligned(16))) unsigned char smem[kStreamBytes > kPartBytes ? kStreamBytes : kPartBytes];
+  __shared__ int32_t lrp[kBlock + 1];  // row bounds relative to the block's first nonzero
+  T *lval = reinterpret_cast<T *>(smem);
+  int32_t *lcol = reinterpret_cast<int32_t *>(smem + kSpmmBlockNnz * sizeof(T));
+  double *part = reinterpret_cast<double *>(smem);
+
+  const int tid = threadIdx.x;
+  const int j = tid & (P - 1), g = tid / P;
+  const int64_t r0 = blocks[2 * blockIdx.x], base = blocks[2 * blockIdx.x + 1];
+  const int64_t r1 = blocks[2 * blockIdx.x + 2];
+  const int64_t cnt = blocks[2 * blockIdx.x + 3] - base;
+  const int nrows = static_cast<int>(r1 - r0);
+  const int cj = panel0 + static_cast<int>(blockIdx.y) * P + j;  // this lane's column of X and Y
+  const bool act = cj < k;
+  const T *__restrict__ xj = X + cj;
+  T *__restrict__ yj = Y + cj;
+
+  if (cnt > kSpmmBlockNnz) {
+    // one long row: the group of stream s adds nonzeros s, s + 64, … ascending
+    double a[NS];
+#pragma unroll
+    for (int u = 0; u < NS; ++u) a[u] = 0.0;
+    if (act) {
+      for (int64_t m0 = 0; m0 < cnt; m0 += kLongStreams) {
+        int32_t c[NS];
+        T v[NS], x[NS];
+#pragma unroll
+        for (int u = 0; u < NS; ++u) {
+          const int64_t m = m0 + g + u * G;
+          c[u] = -1;
+          v[u] = T(0);
+          if (m < cnt) {
+            c[u] = ld_stream(col + base + m);
+            v[u] = ld_stream(val + base + m);
+          }
+        }
+#pragma unroll
+        for (int u = 0; u < NS; ++u) {
+          x[u] = T(0);
+          if (c[u] >= 0) {
+            LHPC_DEVICE_CHECK(c[u] < n_cols);
+            x[u] = xj[static_cast<int64_t>(c[u]) * ldx];
+          }
+        }
+#pragma unroll
+        for (int u = 0; u < NS; ++u)
+          if (c[u] >= 0) a[u] += static_cast<double>(v[u]) * static_cast<double>(x[u]);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < NS; ++u) part[(g + u * G) * P + j] = a[u];
+    __syncthreads();
+    if (g == 0 && act) {
+      double t = part[j];
+      for (int s = 1; s < kLongStreams; ++s) t += part[s * P + j];
+      LHPC_DEVICE_CHECK(r0 < n_rows);
+      const T y = static_cast<T>(t);
+      yj[r0 * ldy] = y;
+      dpart[static_cast<int64_t>(blockIdx.x) * k + cj] = static_cast<double>(W[r0 * ldw + cj]) * static_cast<double>(y);
+    }
+    return;
+  }
+
+  // stream phase: the block's col/val once, coalesced; row bounds with them
+  constexpr int PER = kSpmmBlockNnz / kBlock;
+  {
+    int32_t c[PER];
+    T v[PER];
+#pragma unroll
+    for (int i = 0; i < PER; ++i) {
+      const int64_t m = i * kBlock + tid;
+      c[i] = 0;
+      v[i] = T(0);
+      if (m < cnt) {
+        c[i] = ld_stream(col + base + m);
+        v[i] = ld_stream(val + base + m);
+      }
+    }
+    if (tid <= nrows) lrp[tid] = static_cast<int32_t>(static_cast<int64_t>(row_ptr[r0 + tid]) - base);
+    if (tid == 0 && nrows == kBlock) lrp[kBlock] = static_cast<int32_t>(cnt);
+#pragma unroll
+    for (int i = 0; i < PER; ++i) {
+      const int m = i * kBlock + tid;
+      if (m < cnt) {
+        lcol[m] = c[i];
+        lval[m] = v[i];
+      }
+    }
+  }
+  __syncthreads();
+  // lanes past k stay for the barrier below; row g + t·G is of stream
+  // g + (t mod NS)·G, whose sum is d[t mod NS]
+  double d[NS];
+#pragma unroll
+  for (int u = 0; u < NS; ++u) d[u] = 0.0;
+  if (act) {
+    const T *__restrict__ wj = W + cj;
+    int t = 0;
+    for (int r = g; r < nrows; r += G, ++t) {
+      const T y = spmm_row<T>(lval, lcol, lrp[r], lrp[r + 1], xj, ldx, n_cols);
+      LHPC_DEVICE_CHECK(r0 + r < n_rows);
+      const T w = wj[(r0 + r) * ldw];
+      yj[(r0 + r) * ldy] = y;
+      dot_stream_add<NS>(d, t & (NS - 1), static_cast<double>(w) * static_cast<double>(y));
+    }
+  }
+  __syncthreads();  // every group has left lval / lcol: part takes their place
+  const double bs = dot_streams_sum<P, NS>(d, part, g, j);
+  if (g == 0 && act) dpart[static_cast<int64_t>(blockIdx.x) * k + cj] = bs;
+}
+
+// out[j] = Σ_b part[b·k + j] in a fixed order (one workgroup per column)
+__global__ __launch_bounds__(kBlock) void k_coldot_finish(const double *__restrict__ part, int64_t nb, int k,
+                                                          const int *__restrict__ mode, double *__restrict__ out) {
+  __shared__ double sh[kBlock / kWave];
+  const int j = blockIdx.x;
+  if (mode && mode[j] == 0) return;  // the whole workgroup
+  double v = 0.0;
+  for (int64_t b = threadIdx.x; b < nb; b += kBlock) v += part[b * k + j];
+  for (int o = kWave / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
+  if ((threadIdx.x & (kWave - 1)) == 0) sh[threadIdx.x / kWave] = v;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double t = 0.0;
+    for (int i = 0; i < kBlock / kWave; ++i) t += sh[i];
+    out[j] = t;
+  }
+}
+
+// W = null: k_spmm_csr; else k_spmm_dot with the plan's partials buffer
 template <typename T, typename I, int P>
 int launch_panel(const lhpc_spmm_plan *p, int k, const void *X, int64_t ldx, void *Y, int64_t ldy, int panel0,
-                 int n_panels, hipStream_t s) {
-  hipLaunchKernelGGL((k_spmm_csr<T, I, P>), dim3(static_cast<unsigned>(p->n_blocks), static_cast<unsigned>(n_panels)),
-                     dim3(kBlock), 0, s, static_cast<const I *>(p->d_row_ptr), p->d_col,
-                     static_cast<const T *>(p->d_val), static_cast<const T *>(X), ldx, static_cast<T *>(Y), ldy,
-                     p->d_blocks, p->n_rows, p->n_cols, k, panel0);
+                 int n_panels, const void *W, int64_t ldw, hipStream_t s) {
+  const dim3 grid(static_cast<unsigned>(p->n_blocks), static_cast<unsigned>(n_panels));
+  if (W)
+    hipLaunchKernelGGL((k_spmm_dot<T, I, P>), grid, dim3(kBlock), 0, s, static_cast<const I *>(p->d_row_ptr), p->d_col,
+                       static_cast<const T *>(p->d_val), static_cast<const T *>(X), ldx, static_cast<T *>(Y), ldy,
+                       p->d_blocks, p->n_rows, p->n_cols, k, panel0, static_cast<const T *>(W), ldw,
+                       static_cast<double *>(p->d_dpart));
+  else
+    hipLaunchKernelGGL((k_spmm_csr<T, I, P>), grid, dim3(kBlock), 0, s, static_cast<const I *>(p->d_row_ptr), p->d_col,
+                       static_cast<const T *>(p->d_val), static_cast<const T *>(X), ldx, static_cast<T *>(Y), ldy,
+                       p->d_blocks, p->n_rows, p->n_cols, k, panel0);
   return check_launch(s);
 }
 
 // full panels of kSpmmPanelMax columns in one launch (blockIdx.y = panel), then
 // the remaining columns in a launch of the narrowest panel that holds them
 template <typename T, typename I>
-int launch_spmm(const lhpc_spmm_plan *p, int k, const void *X, int64_t ldx, void *Y, int64_t ldy, hipStream_t s) {
+int launch_spmm(const lhpc_spmm_plan *p, int k, const void *X, int64_t ldx, void *Y, int64_t ldy, const void *W,
+                int64_t ldw, hipStream_t s) {
   const int full = k / kSpmmPanelMax, rest = k % kSpmmPanelMax;
   if (full > 65535) return LHPC_ERR_UNSUPPORTED;  // gridDim.y
-  if (full > 0) LHPC_TRY((launch_panel<T, I, kSpmmPanelMax>(p, k, X, ldx, Y, ldy, 0, full, s)));
+  if (full > 0) LHPC_TRY((launch_panel<T, I, kSpmmPanelMax>(p, k, X, ldx, Y, ldy, 0, full, W, ldw, s)));
   const int p0 = full * kSpmmPanelMax;
   if (rest == 0) return LHPC_OK;
-  if (rest <= 4) return launch_panel<T, I, 4>(p, k, X, ldx, Y, ldy, p0, 1, s);
-  if (rest <= 8) return launch_panel<T, I, 8>(p, k, X, ldx, Y, ldy, p0, 1, s);
-  if (rest <= 16) return launch_panel<T, I, 16>(p, k, X, ldx, Y, ldy, p0, 1, s);
-  return launch_panel<T, I, 32>(p, k, X, ldx, Y, ldy, p0, 1, s);
+  if (rest <= 4) return launch_panel<T, I, 4>(p, k, X, ldx, Y, ldy, p0, 1, W, ldw, s);
+  if (rest <= 8) return launch_panel<T, I, 8>(p, k, X, ldx, Y, ldy, p0, 1, W, ldw, s);
+  if (rest <= 16) return launch_panel<T, I, 16>(p, k, X, ldx, Y, ldy, p0, 1, W, ldw, s);
+  return launch_panel<T, I, 32>(p, k, X, ldx, Y, ldy, p0, 1, W, ldw, s);
 }
 
-int launch(const lhpc_spmm_plan *p, int k, const void *X, int64_t ldx, void *Y, int64_t ldy, hipStream_t s) {
+int launch(const lhpc_spmm_plan *p, int k, const void *X, int64_t ldx, void *Y, int64_t ldy, hipStream_t s,
+           const void *W = nullptr, int64_t ldw = 0) {
   if (p->n_blocks == 0) return LHPC_OK;
   if (p->dtype == LHPC_F32)
-    return p->rp64 ? launch_spmm<float, int64_t>(p, k, X, ldx, Y, ldy, s)
-                   : launch_spmm<float, int32_t>(p, k, X, ldx, Y, ldy, s);
-  return p->rp64 ? launch_spmm<double, int64_t>(p, k, X, ldx, Y, ldy, s)
-                 : launch_spmm<double, int32_t>(p, k, X, ldx, Y, ldy, s);
+    return p->rp64 ? launch_spmm<float, int64_t>(p, k, X, ldx, Y, ldy, W, ldw, s)
+                   : launch_spmm<float, int32_t>(p, k, X, ldx, Y, ldy, W, ldw, s);
+  return p->rp64 ? launch_spmm<double, int64_t>(p, k, X, ldx, Y, ldy, W, ldw, s)
+                 : launch_spmm<double, int32_t>(p, k, X, ldx, Y, ldy, W, ldw, s);
 }
 
 // host ↔ device copy of an `rows` × k block with leading dimensions (elements)
@@ -234,7 +417,9 @@ int copy_block(void *dst, int64_t ldd, const void *src, int64_t lds, int64_t row
   return LHPC_OK;
 }
 
-int grow(void **buf, size_t &have, size_t want, int64_t &acct) {
+}  // namespace
+
+int spmm_grow(void **buf, size_t &have, size_t want, int64_t &acct) {
   if (want <= have && *buf) return LHPC_OK;
   if (*buf) {
     LHPC_HIP_TRY(hipFree(*buf));
@@ -246,6 +431,17 @@ int grow(void **buf, size_t &have, size_t want, int64_t &acct) {
   have = std::max<size_t>(want, 16);
   return LHPC_OK;
 }
+
+int spmm_dot_reserve(lhpc_spmm_plan *p, int k) {
+  return spmm_grow(&p->d_dpart, p->dpart_bytes, static_cast<size_t>(p->n_blocks) * k * sizeof(double), p->bytes);
+}
+
+int coldot_finish_launch(const double *part, int64_t n_units, int k, const int *mode, double *out, hipStream_t s) {
+  hipLaunchKernelGGL(k_coldot_finish, dim3(static_cast<unsigned>(k)), dim3(kBlock), 0, s, part, n_units, k, mode, out);
+  return check_launch(s);
+}
+
+namespace {
 
 int plan_build(lhpc_spmm_plan *p, const void *row_ptr, int bits, const int32_t *col_idx, const void *val,
                bool device_input) {
@@ -344,12 +540,27 @@ extern "C" int lhpc_spmm(lhpc_spmm_plan *p, int k, const void *X, int64_t ldx, v
     // host buffers: synchronous strided copies through packed plan-owned
     // buffers, which only host-buffer calls touch (they end synchronised)
     const size_t tsz = p->dtype == LHPC_F32 ? 4 : 8;
-    LHPC_TRY(grow(&p->d_xstage, p->xstage_bytes, static_cast<size_t>(p->n_cols) * k * tsz, p->bytes));
-    LHPC_TRY(grow(&p->d_ystage, p->ystage_bytes, static_cast<size_t>(p->n_rows) * k * tsz, p->bytes));
+    LHPC_TRY(spmm_grow(&p->d_xstage, p->xstage_bytes, static_cast<size_t>(p->n_cols) * k * tsz, p->bytes));
+    LHPC_TRY(spmm_grow(&p->d_ystage, p->ystage_bytes, static_cast<size_t>(p->n_rows) * k * tsz, p->bytes));
     LHPC_TRY(copy_block(p->d_xstage, k, X, ldx, p->n_cols, k, tsz, hipMemcpyHostToDevice));
     LHPC_TRY(launch(p, k, p->d_xstage, k, p->d_ystage, k, s));
     LHPC_HIP_TRY(hipStreamSynchronize(s));
     return copy_block(Y, ldy, p->d_ystage, k, p->n_rows, k, tsz, hipMemcpyDeviceToHost);
+  } LHPC_ABI_CATCH
+}
+
+extern "C" int lhpc_spmm_dot(lhpc_spmm_plan *p, int k, const void *X, int64_t ldx, void *Y, int64_t ldy,
+                             const void *W, int64_t ldw, double *dots, void *stream) {
+  try {
+    // sizes first, the plan is read after them
+    if (!p || k < 1 || ldx < k || ldy < k || ldw < k) return LHPC_ERR_INVALID_ARG;
+    if (!X || !Y || !W || !dots) return LHPC_ERR_INVALID_ARG;
+    RocTxRange rx("lhpc_spmm_dot");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    LHPC_HIP_TRY(hipSetDevice(p->device));
+    LHPC_TRY(spmm_dot_reserve(p, k));  // allocates only when k outgrows the buffer
+    LHPC_TRY(launch(p, k, X, ldx, Y, ldy, s, W, ldw));
+    return coldot_finish_launch(static_cast<const double *>(p->d_dpart), p->n_blocks, k, nullptr, dots, s);
   } LHPC_ABI_CATCH
 }
 
@@ -374,8 +585,9 @@ extern "C" int lhpc_spmm_plan_destroy(lhpc_spmm_plan *p) {
     if (!p) return LHPC_OK;
     (void)hipSetDevice(p->device);
     for (void *q : {p->d_row_ptr, static_cast<void *>(p->d_col), p->d_val, static_cast<void *>(p->d_blocks),
-                    p->d_xstage, p->d_ystage})
+                    p->d_xstage, p->d_ystage, p->d_dpart, p->cg_vecs, p->cg_scal})
       if (q) (void)hipFree(q);
+    if (p->cg_host) (void)hipHostFree(p->cg_host);
     delete p;
     return LHPC_OK;
   } LHPC_ABI_CATCH
