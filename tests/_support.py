@@ -212,3 +212,53 @@ def sampled_rows_fp64(rp, col, val, x, m, seed=0x5EED00C1):
     seg = np.repeat(np.arange(rows.size), lens)
     return rows, np.bincount(seg, weights=prod, minlength=rows.size), \
         np.bincount(seg, weights=np.abs(prod), minlength=rows.size)
+
+
+# ------------------------------------------------------------ non-finite x
+def row_sums_fp64(rp, col, val, x):
+    """fp64 numpy row sums of val·x[col] (no oracle/ code), empty rows 0.
+    Used for where a non-finite x must show up in y: whether a row's sum is
+    NaN or ±inf does not depend on the order of its additions."""
+    n = rp.shape[0] - 1
+    e = np.zeros(n, dtype=np.float64)
+    nz = np.diff(rp) > 0
+    with np.errstate(invalid="ignore", over="ignore"):
+        prod = val.astype(np.float64) * x.astype(np.float64)[col]
+        if nz.any():
+            e[nz] = np.add.reduceat(prod, rp[:-1][nz].astype(np.int64))
+    return e
+
+
+def plant_column(rp, col, row, c, where="first", protect=()):
+    """Give `row` an entry at column c in place of its first / last one that
+    is not in `protect`, keeping the row sorted and distinct (in place; the
+    row length stays)."""
+    s, t = int(rp[row]), int(rp[row + 1])
+    seg = col[s:t]
+    if c in seg:
+        return
+    free = np.nonzero(~np.isin(seg, list(protect)))[0]
+    assert free.size, f"row {row} has no entry to give up"
+    drop = free[0] if where == "first" else free[-1]
+    col[s:t] = np.sort(np.append(np.delete(seg, drop), c)).astype(col.dtype)
+
+
+def assert_nonfinite_stays(y, y_clean, e):
+    """y = A·x for an x with NaN / Inf entries against y_clean = A·x_clean
+    (the same plan's, the poisoned entries replaced by finite ones) and
+    e = row_sums_fp64 on the poisoned x: rows whose e is finite keep y_clean's
+    bits; the others are NaN where e is NaN and equal e where it is ±inf."""
+    aff = ~np.isfinite(e)
+    bad = np.nonzero(~aff & ~((y == y_clean) & (np.signbit(y) == np.signbit(y_clean))))[0]
+    assert bad.size == 0, (f"{bad.size} rows without a poisoned entry changed; first row {bad[0]}: "
+                           f"got {y[bad[0]]!r} want {y_clean[bad[0]]!r}")
+    wrong = np.nonzero(aff & (np.isnan(y) != np.isnan(e)))[0]
+    assert wrong.size == 0, f"row {wrong[0]}: got {y[wrong[0]]!r}, fp64 row sum {e[wrong[0]]!r}"
+    inf = np.isinf(e)
+    assert np.array_equal(y[inf].astype(np.float64), e[inf]), "a row whose sum is ±inf lost it"
+    return aff
+
+
+def touches_unaffected_neighbour(aff):
+    """some row without a poisoned entry lies directly next to one with"""
+    return bool(np.any(aff[1:] != aff[:-1]))

@@ -315,3 +315,72 @@ def test_cpp_drop_in(gpu, tmp_path):
                    check=True, timeout=300)
     r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and "spmm cpp api: ok" in r.stdout, (r.returncode, r.stdout[-500:], r.stderr[-2000:])
+
+
+# ------------------------------------------------------------------ non-finite X
+_NAN_CASES = {}
+
+
+def _nan_case(lhpc, matrix, dt):
+    """(row_ptr, col_idx, val, n_cols, poisoned columns): dyadic values; the
+    poisoned columns of x — the first, the last, 63 / 64 and an interior one —
+    have entries planted in chosen rows (rows of 1, of 15, the 2048-, a 2049-
+    and the 10 000-entry row), so nothing is left to chance."""
+    if (matrix, dt) not in _NAN_CASES:
+        if matrix == "uniform4099":
+            m = 4099
+            rp, col, val = lhpc.gen_uniform_csr(m, m, 15, dtype=dt, dist=1, seed=0xED00)
+            targets = [(10, 2000), (12, 2002), (14, 2004), (16, 2006), (18, 2008)]
+        else:
+            rp, col, val, m = _long_row_csr(lhpc, dt, 1, 0xED01)
+            targets = [(0, 1, 20), (1, 22), (4, 24), (7, 26), (7, 10, 28)]  # row 1: 2048, 4: 2049, 7: 10 000 entries
+        col = col.copy()
+        poison = [0, m - 1, 63, 64, (m // 2) | 1]
+        for k, (c, rows) in enumerate(zip(poison, targets)):
+            for r in rows:
+                S.plant_column(rp, col, r, c, "first" if k % 2 == 0 else "last", protect=poison)
+        for r in range(rp.size - 1):
+            assert (np.diff(col[rp[r]:rp[r + 1]]) > 0).all()
+        _NAN_CASES[(matrix, dt)] = (rp, col, val, m, np.array(poison))
+    return _NAN_CASES[(matrix, dt)]
+
+
+@pytest.mark.parametrize("dtype", ["f32", "f64"])
+@pytest.mark.parametrize("k,j0", [(5, 0), (5, 4), (33, 0), (33, 31), (33, 32)])
+@pytest.mark.parametrize("matrix", ["uniform4099", "longrows"])
+def test_nan_in_one_column_of_x_stays_there(lhpc, gpu, matrix, k, j0, dtype):
+    """NaN in X[c, j0] for a few columns c of A, in one column j0 of the block
+    only (the first and the last of a panel, and of the 1-wide tail panel of
+    k = 33): every other column of Y keeps the clean call's bits (clean: those
+    entries 0.5; checked against the oracle), column j0 is NaN exactly in the
+    rows whose fp64 row sum is (tests/_support.py assert_nonfinite_stays).
+    lhpc_spmm_dot on the same inputs stores the same Y, and its dots[j] for
+    j != j0 keep the clean call's bits while dots[j0] is NaN.  A panel-tail
+    lane or a padded product that read another column's x would show."""
+    import torch
+    dt = _dt(lhpc, dtype)
+    rp, col, val, m, poison = _nan_case(lhpc, matrix, dt)
+    n = rp.shape[0] - 1
+    Xc = _block(lhpc, dt, 1, m, k, 0xED10 + k)
+    Xc[poison, j0] = 0.5
+    Xb = Xc.copy()
+    Xb[poison, j0] = np.nan
+    W = _block(lhpc, dt, 1, n, k, 0xED20 + k)
+    e = S.row_sums_fp64(rp, col, val, np.ascontiguousarray(Xb[:, j0]))
+    with lhpc.SpMMPlan(rp, col, val, m) as plan:
+        xc, xb, w = (torch.from_numpy(a).to(gpu) for a in (Xc, Xb, W))
+        nan_y = lambda: torch.full((n, k), float("nan"), dtype=xc.dtype, device=gpu)  # noqa: E731
+        Yb = plan(xb, nan_y()).cpu().numpy()
+        Yc = plan(xc, nan_y()).cpu().numpy()  # after the poisoned call, on the same plan
+        Ydb, dots_b = lhpc.spmm_dot(plan, xb, w, nan_y())
+        Ydc, dots_c = lhpc.spmm_dot(plan, xc, w, nan_y())
+        Ydb, Ydc, dots_b, dots_c = (t.cpu().numpy() for t in (Ydb, Ydc, dots_b, dots_c))
+    cols = sorted({0, j0, k - 1})
+    _check_block(rp, col, val, Xc[:, cols], Yc[:, cols], True)
+    others = [j for j in range(k) if j != j0]
+    assert np.array_equal(Yb[:, others], Yc[:, others]), "NaN in one column of X changed another column of Y"
+    aff = S.assert_nonfinite_stays(Yb[:, j0], Yc[:, j0], e)
+    assert aff.sum() >= 5 and aff.mean() <= 0.10 and S.touches_unaffected_neighbour(aff)
+    assert np.array_equal(Ydb, Yb, equal_nan=True) and np.array_equal(Ydc, Yc)
+    assert np.array_equal(dots_b[others], dots_c[others]) and np.isnan(dots_b[j0])
+    assert np.isfinite(dots_c).all()

@@ -1059,3 +1059,307 @@ def test_xtile_layout_pinned(lhpc, gpu, name):
         assert got[build]["info"]["kernel"] == lhpc.KERNEL_XTILE
         for key in ("digest", "info", "y_sha256"):
             assert got[build][key] == want[build][key], (build, key)
+
+
+# ------------------------------------------------------------------ XSLICE variants
+XS = FAMILIES["xslice"]
+_UNIFORM_CASES = {}
+
+
+def _uniform_case(lhpc, n, dt, dist):
+    """min(n, 15) uniform nonzeros per row, n × n, with its x and oracle, built once."""
+    key = (n, dt, dist)
+    if key not in _UNIFORM_CASES:
+        rp, col, val = lhpc.gen_uniform_csr(n, n, min(n, 15), dtype=dt, dist=dist, seed=0xF000 + n)
+        x = lhpc.gen_values(dt, dist, n, 0xF100 + n)
+        _UNIFORM_CASES[key] = (rp, col, val, x, S.spmv_oracle(rp, col, val, x))
+    return _UNIFORM_CASES[key]
+
+
+@pytest.mark.parametrize("dtype", ["f32", "f64"])
+@pytest.mark.parametrize("slices", [1, 3, 7, 8, 12, 16, 24])
+def test_xslice_slice_counts(lhpc, gpu, slices, dtype):
+    """options.xslice_slices: the S < 8 block mapping (s = b % S), one phase
+    (S = 8) and several phases (S = 16, 24: idx / blocks_per_slice; 12 is
+    rounded up to 16), on one row, a partial chunk, several workgroups per
+    slice (4099 rows: 65 chunks, 17 blocks) and slices left without columns
+    (n < 64·S).  Dyadic: bit-exact; U[-1, 1): within the bar."""
+    dt = lhpc.F32 if dtype == "f32" else lhpc.F64
+    for n in (1, 65, 257, 1000, 4099):
+        for dist in (1, 0):
+            rp, col, val, x, (y64, yr, asum) = _uniform_case(lhpc, n, dt, dist)
+            y, info = _run(lhpc, gpu, rp, col, val, x, n, XS, options={"xslice_slices": slices})
+            assert info["kernel"] == lhpc.KERNEL_XSLICE
+            assert info["slices"] == (slices if slices <= 8 else -(-slices // 8) * 8), info
+            if dist == 1:
+                assert np.array_equal(y, yr), (n, slices)
+            else:
+                S.assert_spmv_close(y, y64, asum)
+
+
+_WINDOW_CSR = []
+
+
+def _xslice_window_csr():
+    """(row_ptr, col_idx, n_cols) of the window-loop matrix: 3000 rows over
+    20 000 columns, distinct sorted columns per row.  Background rows of 0, 1,
+    2 and 5 nonzeros; `band` rows draw their columns from a 2000-column band
+    that lies inside one slice for S = 3 and S = 8 (so they keep their whole
+    length in it), the others from all of x."""
+    if _WINDOW_CSR:
+        return _WINDOW_CSR[0]
+    rng = np.random.default_rng(0xC200)
+    n_rows, n_cols = 3000, 20_000
+    bands = (0, 7680)  # S = 3: slices 0 / 1 (width 6720); S = 8: slices 0 / 3 (width 2560)
+    lens = rng.choice([0, 1, 1, 2, 5], size=n_rows).astype(np.int64)
+    band = np.full(n_rows, -1)
+
+    def put(chunk, rows, b):
+        for r, ln in rows:
+            lens[chunk * 64 + r], band[chunk * 64 + r] = ln, b
+
+    for i, ch in enumerate((3, 11, 19)):  # chunks of > 64 in-slice nonzeros
+        put(ch, [(5, 40 + 4 * i), (30, 48)], i % 2)
+    for i, ch in enumerate((5, 13, 21)):  # > 128
+        put(ch, [(1, 41), (2, 48), (40, 44), (63, 47)], i % 2)
+    for i, ch in enumerate((7, 15, 23)):  # > 256: wave-reduced rows (49, 100) across window edges
+        put(ch, [(0, 48), (1, 45), (2, 49), (3, 100), (20, 42), (62, 46), (63, 49)], i % 2)
+    put(0, [(0, 49)], 0)
+    put(46, [(55, 100)], 1)  # the last row
+    put(31, [(7, 300)], 0)  # 300 in one slice: uint16 lengths
+    lens[1000:1003] = (100, 49, 48)  # over all of x: short in every slice
+    lens[2000] = 5000
+    cols = []
+    for ln, b in zip(lens, band):
+        if ln:
+            c = np.sort(rng.choice(2000 if b >= 0 else n_cols, size=int(ln), replace=False))
+            cols.append((c + (bands[b] if b >= 0 else 0)).astype(np.int32))
+    rp = np.zeros(n_rows + 1, dtype=np.int32)
+    np.cumsum(lens, out=rp[1:])
+    _WINDOW_CSR.append((rp, np.concatenate(cols), n_cols))
+    return _WINDOW_CSR[0]
+
+
+def _xslice_window_values(dtype, dyadic):
+    rp, col, n_cols = _xslice_window_csr()
+    rng = np.random.default_rng(0xC201 + dyadic)
+    if dyadic:
+        val = (rng.integers(-8, 9, size=col.size) / 8.0).astype(dtype)
+        x = (rng.integers(-8, 9, size=n_cols) / 8.0).astype(dtype)
+    else:
+        val = rng.uniform(-1.0, 1.0, size=col.size).astype(dtype)
+        x = rng.uniform(-1.0, 1.0, size=n_cols).astype(dtype)
+    return val, x
+
+
+@pytest.mark.parametrize("slices", [3, 8])
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_xslice_windows(lhpc, gpu, dtype, slices):
+    """options.xslice_window = NB pins the stream kernel's window of NB·64
+    nonzeros (k_spmv_xslice_stream<…, NB>; not visible in the plan info: read
+    from launch_xslice, which switches on the plan's xs_nb = the option).  One
+    matrix whose 64-row chunks hold more than 64, 128 and 256 in-slice
+    nonzeros, so every window size loops; lane-summed rows (≤ kLongRow = 48 in
+    the slice) and wave-reduced rows (49, 100, 300) that span window edges; a
+    300-entry row in one slice (uint16 lengths) and a 5000-entry row.  The
+    structure is asserted, not assumed.  Dyadic: bit-exact against the oracle,
+    so identical across the four windows; U[-1, 1): within the bar."""
+    rp, col, n_cols = _xslice_window_csr()
+    n = rp.size - 1
+    width = ((n_cols + slices - 1) // slices + 63) // 64 * 64  # build_xslice: ⌈n_cols / S⌉ rounded up to 64
+    cnt = np.bincount(np.repeat(np.arange(n), np.diff(rp)) * slices + col // width, minlength=n * slices)
+    cnt = cnt.reshape(n, slices)
+    assert cnt.max() >= 300 and (cnt == 49).any() and (cnt == 100).any() and ((cnt >= 40) & (cnt <= 48)).any()
+    assert (np.diff(rp) == 0).any() and (np.diff(rp) == 1).any()
+    chunk = np.add.reduceat(cnt, np.arange(0, n, 64), axis=0)  # in-slice nonzeros per (64-row chunk, slice)
+    for cap in (64, 128, 256):
+        assert (chunk > cap).sum() >= 3, cap
+    for dyadic in (True, False):
+        val, x = _xslice_window_values(dtype, dyadic)
+        y64, yr, asum = S.spmv_oracle(rp, col, val, x)
+        ys = []
+        for window in (1, 2, 3, 4):
+            y, info = _run(lhpc, gpu, rp, col, val, x, n_cols, XS,
+                           options={"xslice_slices": slices, "xslice_window": window})
+            assert info["kernel"] == lhpc.KERNEL_XSLICE and info["slices"] == slices
+            assert info["slice_width"] == width
+            if dyadic:
+                assert np.array_equal(y, yr), window
+            else:
+                S.assert_spmv_close(y, y64, asum)
+            ys.append(y)
+        if dyadic:
+            assert all(np.array_equal(y, ys[0]) for y in ys[1:]), "y depends on the window"
+
+
+@pytest.mark.parametrize("slices", [3, 8])
+def test_xslice_partial_option(lhpc, gpu, slices):
+    """options.xslice_partial on fp32: 2 (fp64 partials) is the
+    LHPC_PLAN_EXACT_PARTIALS plan and 1 (fp32) the LHPC_PLAN_FAST_PARTIALS
+    plan, bit for bit on U[-1, 1) values; the fp64-partial plan holds 4 B ×
+    slices × padded rows more.  fp64 partials meet the header's bound
+    |y − y64| ≤ 2^-24·|y64| + 2^-40·Σ|a·x| (2^-24|y| + O(2^-50)·Σ|a·x| with
+    2^10 of room for the O()); fp32 partials stay within the 1e-6 bar."""
+    rp, col, n_cols = _xslice_window_csr()
+    n = rp.size - 1
+    val, x = _xslice_window_values(np.float32, False)
+    y64, _, asum = S.spmv_oracle(rp, col, val, x)
+    o = {"xslice_slices": slices}
+    y2, i2 = _run(lhpc, gpu, rp, col, val, x, n_cols, XS, options=dict(o, xslice_partial=2))
+    ye, ie = _run(lhpc, gpu, rp, col, val, x, n_cols, FAMILIES["xslice_exact"], options=o)
+    y1, i1 = _run(lhpc, gpu, rp, col, val, x, n_cols, XS, options=dict(o, xslice_partial=1))
+    yf, if_ = _run(lhpc, gpu, rp, col, val, x, n_cols, FAMILIES["xslice_fast"], options=o)
+    for info in (i2, ie, i1, if_):
+        assert info["kernel"] == lhpc.KERNEL_XSLICE and info["slices"] == slices
+    assert np.array_equal(y2, ye) and np.array_equal(y1, yf)
+    more = 4 * slices * (-(-n // 64) * 64)
+    assert i2["device_bytes"] - i1["device_bytes"] == more and ie["device_bytes"] - if_["device_bytes"] == more
+    err = np.abs(y2.astype(np.float64) - y64)
+    bound = 2.0 ** -24 * np.abs(y64) + 2.0 ** -40 * asum
+    worst = int(np.argmax(err - bound))
+    print(f"\nxslice_partial=2, S={slices}: max err/bound {np.max(err / np.maximum(bound, 1e-300)):.3f}")
+    assert (err <= bound).all(), (worst, err[worst], bound[worst])
+    S.assert_spmv_close(y1, y64, asum)
+
+
+def test_xslice_mb_option(lhpc, gpu):
+    """options.xslice_mb (the x bytes one slice may span): 20 000 rows over
+    1.5M columns (x = 6 MB, fp32, 15 per row) give the default's 8 slices and,
+    at 0.25 MB, 8·⌈6 MB / (8 · 0.25 MB)⌉ = 24 (xslice_build); both bit-exact."""
+    n, m = 20_000, 1_500_000
+    rp, col, val = lhpc.gen_uniform_csr(n, m, 15, dtype=lhpc.F32, dist=1, seed=0xF200)
+    x = lhpc.gen_values(lhpc.F32, 1, m, 0xF201)
+    yr = S.spmv_oracle(rp, col, val, x)[1]
+    for opts, slices in ((None, 8), ({"xslice_mb": 0.25}, 24)):
+        y, info = _run(lhpc, gpu, rp, col, val, x, m, XS, options=opts)
+        assert info["kernel"] == lhpc.KERNEL_XSLICE and info["slices"] == slices, info
+        assert np.array_equal(y, yr)
+
+
+# ------------------------------------------------------------------ non-finite x
+NF_LENGTHS = [20000] + [3] * 50 + [5000, 4096, 4095, 1, 0, 9000] + [15] * 3000 + [0, 0] + [30000] + [7] * 4000
+NF_ROWS3, NF_ROWS15, NF_ROW4096, NF_ROW30000 = (2, 4, 6, 8, 10), (100, 102, 104, 106, 108), 52, 3059
+# name: (plan flags, options, kernel family)
+NF_CASES = {
+    "rowgroup": (FAMILIES["rowgroup"], None, "ROWGROUP"),
+    "adaptive": (FAMILIES["adaptive"], None, "ADAPTIVE"),
+    "xslice8": (XS, {"xslice_slices": 8}, "XSLICE"),
+    "xslice3": (XS, {"xslice_slices": 3}, "XSLICE"),
+    "sell": (1 << 10, None, "SELL"),
+    "xtile_perm": (FAMILIES["xtile"], {"xtile_reduce": 1, "xtile_align": 1}, "XTILE"),
+    "xtile_iperm": (FAMILIES["xtile"], {"xtile_reduce": 2, "xtile_align": 1}, "XTILE"),
+    "xtile_iperm_aligned": (FAMILIES["xtile"], {"xtile_reduce": 2, "xtile_align": 2}, "XTILE"),
+    "xtile_ranges3": (FAMILIES["xtile"], {"xtile_ranges": 3}, "XTILE"),
+    "xtile_col_blocks3": (FAMILIES["xtile"], {"xtile_col_blocks": 3}, "XTILE"),
+    "xtile_part_nnz": (FAMILIES["xtile"], {"xtile_part_nnz": 40_000}, "XTILE"),
+    "xtile_pretable1": (FAMILIES["xtile"], {"xtile_reduce": 2, "xtile_pretable": 1}, "XTILE"),
+    "xtile_pretable2": (FAMILIES["xtile"], {"xtile_reduce": 2, "xtile_pretable": 2}, "XTILE"),
+}
+_NF_BASE = {}
+
+
+def _nf_base(sell):
+    """(row_ptr, col_idx, dyadic fp64 values, dyadic fp64 x, n_cols) before the
+    poisoned columns are planted, built once."""
+    if sell not in _NF_BASE:
+        if sell:
+            rng = np.random.default_rng(0xD300)
+            n = n_cols = 10_003
+            lens = rng.integers(0, 9, size=n)
+            rp = np.zeros(n + 1, dtype=np.int32)
+            np.cumsum(lens, out=rp[1:])
+            col = np.concatenate([min(max(i - 20, 0), n - 41) + np.sort(rng.choice(41, size=int(ln), replace=False))
+                                  for i, ln in enumerate(lens)]).astype(np.int32)  # within 40 of the diagonal
+            val = rng.integers(-8, 9, size=col.size) / 8.0
+        else:
+            n_cols = 200_000
+            rp, col, val = _csr_from_lengths(NF_LENGTHS, n_cols, 0xD301, dyadic=True)
+        x = np.random.default_rng(0xD302).integers(-8, 9, size=n_cols) / 8.0
+        _NF_BASE[sell] = (rp, col, val, x, n_cols)
+    return _NF_BASE[sell]
+
+
+def _nf_matrix(sell, w):
+    """The base matrix with the poisoned columns — 0, n_cols − 1, w − 1, w
+    (either side of the first slice / tile edge) and an interior one — planted
+    into chosen rows, and those columns."""
+    rp, col, val, x, n_cols = _nf_base(sell)
+    col = col.copy()
+    poison = [0, n_cols - 1, w - 1, w, (n_cols // 2) | 1]
+    assert len(set(poison)) == 5 and 0 < w < n_cols - 1
+    lens = np.diff(rp)
+    for k, c in enumerate(poison):
+        where = "first" if k % 2 == 0 else "last"
+        if sell:  # three non-empty rows near the column, every other row
+            near = [r for r in range(max(c - 12, 0), min(c + 13, rp.size - 1), 2) if lens[r] > 0][:3]
+            assert len(near) == 3
+            for r in near:
+                S.plant_column(rp, col, r, c, where, protect=poison)
+        else:  # a 3-entry row, a 15-entry row, the 4096 row, the 30000 row
+            for r in (NF_ROWS3[k], NF_ROWS15[k], NF_ROW4096, NF_ROW30000):
+                S.plant_column(rp, col, r, c, where, protect=poison)
+    for r in range(rp.size - 1):  # still CSR with sorted, distinct columns
+        seg = col[rp[r]:rp[r + 1]]
+        assert (np.diff(seg) > 0).all()
+    return rp, col, val, x, n_cols, np.array(poison)
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+@pytest.mark.parametrize("case", list(NF_CASES))
+def test_nonfinite_x_stays_in_its_rows(lhpc, gpu, case, dtype):
+    """Every padded layout relies on "padding contributes 0·0" (SELL's col −1,
+    XTILE's zero slot and zero-padded value runs, XSLICE's clamped loads); a
+    padded entry that read a real x[c] would still add 0·x[c] = 0 for finite
+    x.  Here x holds NaN (then +Inf) at column 0, the last column, the two
+    columns either side of the first slice / x-tile edge (plan info
+    slice_width; for families without one, and plans of parts: the fp32 / fp64
+    tile width 40960 / 20480, SELL: 64, the edge of a wave's own x window) and
+    an interior column; the matrix has entries there in chosen rows (a 3-, a
+    15-, the 4096- and the 30000-entry row; SELL: rows near the column).  y is
+    pre-filled with NaN.  Rows without a poisoned entry must equal, bit for
+    bit, the same plan's y on the clean x (poisoned entries 0.5; checked
+    against the oracle); rows with one are NaN / ±inf exactly where the fp64
+    row sums are.  Then the clean x on the same plan equals a fresh plan's y:
+    nothing non-finite survives in plan-owned buffers (xg rings, carries,
+    partials)."""
+    import torch
+    flags, opts, family = NF_CASES[case]
+    sell = family == "SELL"
+    kernel = getattr(lhpc, "KERNEL_" + family)
+    tdt = torch.float32 if dtype == np.float32 else torch.float64
+
+    def plan_for(rp, col, val, n_cols):
+        p = lhpc.SpMVPlan(rp, col, val, n_cols, flags=flags, options=opts)
+        assert p.info()["kernel"] == kernel, p.info()
+        return p
+
+    def call(plan, x):
+        y = torch.full((plan.n_rows,), float("nan"), dtype=tdt, device=gpu)
+        plan(torch.from_numpy(x).to(gpu), y)
+        return y.cpu().numpy()
+
+    rp, col, val, _, n_cols = _nf_base(sell)
+    with plan_for(rp, col, val.astype(dtype), n_cols) as probe:
+        w0 = probe.info()["slice_width"]
+    w = w0 if 64 <= w0 < n_cols - 1 else (64 if sell else 40960 if dtype == np.float32 else 20480)
+    rp, col, val, x, n_cols, poison = _nf_matrix(sell, w)
+    val = val.astype(dtype)
+    x_clean = x.astype(dtype)
+    x_clean[poison] = 0.5
+    y64, yr, _ = S.spmv_oracle(rp, col, val, x_clean)
+    with plan_for(rp, col, val, n_cols) as fresh:
+        assert fresh.info()["slice_width"] == w0  # planting moved no edge
+        y_clean = call(fresh, x_clean)
+    assert np.array_equal(y_clean, yr)
+    with plan_for(rp, col, val, n_cols) as plan:
+        for bad in (np.nan, np.inf):
+            x_bad = x_clean.copy()
+            x_bad[poison] = bad
+            e = S.row_sums_fp64(rp, col, val, x_bad)
+            aff = S.assert_nonfinite_stays(call(plan, x_bad), y_clean, e)
+            assert aff.sum() >= 10 and aff.mean() <= 0.10, (aff.sum(), aff.mean())
+            assert S.touches_unaffected_neighbour(aff)
+            if np.isinf(bad):
+                assert np.isinf(e).any()
+            y_after = call(plan, x_clean)
+            assert np.array_equal(y_after, y_clean), f"a clean call after x = {bad} differs from a fresh plan's"
