@@ -7,6 +7,7 @@
 
 #include <algorithm>
 #include <cstring>
+#include <iterator>
 #include <vector>
 
 #include "../../include/lhpc.h"
@@ -193,6 +194,62 @@ XtilePartition xtile_partition_policy(int64_t n_rows, int64_t n_cols, int64_t nn
   r.col_blocks = n_splits == 0 ? xtile_col_blocks_for(n_rows, n_cols, nnz, r.tiles, o) : 1;
   r.parts = (nnz > r.cap || r.col_blocks > 1) && n_splits == 0 &&
             (r.tiles + r.col_blocks - 1) / r.col_blocks <= kXtMaxTiles;
+  return r;
+}
+
+constexpr unsigned kForceFamily = LHPC_PLAN_FORCE_ROWGROUP | LHPC_PLAN_FORCE_ADAPTIVE | LHPC_PLAN_FORCE_XSLICE |
+                                  LHPC_PLAN_FORCE_XTILE | LHPC_PLAN_FORCE_SELL;
+
+bool spmv_wants_locality(int64_t n_cols, size_t elem_bytes, unsigned flags) {
+  return !(flags & kForceFamily) && static_cast<double>(n_cols) * static_cast<double>(elem_bytes) > 8.0e6;
+}
+
+SpmvFamilyPolicy spmv_family_policy(const SpmvShape &s, unsigned flags, const lhpc_options &o) {
+  SpmvFamilyPolicy r;
+  const bool auto_ok = !(flags & kForceFamily);
+  // XTILE / XSLICE when x outgrows one XCD's 4 MB L2, and only when the
+  // gathers have no locality of their own: a banded or structured matrix
+  // (stencil operators, the CG Laplacian) re-reads each x line from
+  // neighbouring rows, which the row-local kernels already serve from L2,
+  // while XSLICE would add S partials per row.  Measured: distinct 128-B x
+  // lines per nonzero over sampled 8192-row chunks (≈0.8 for C2's uniform
+  // columns, ≈0.03 for a 2-D Laplacian); ≤ 0.25 counts as local.
+  const double locality_thr = o.spmv_locality > 0 ? o.spmv_locality : 0.25;
+  const bool nolocal = spmv_wants_locality(s.n_cols, s.elem_bytes, flags) && s.lines_per_nnz > locality_thr;
+  // XTILE (x tiles in LDS) is the default for gathers without locality;
+  // options.spmv_no_xtile selects XSLICE instead.  A layout that does not fit
+  // its index types, or a row too long for one slice, falls through.
+  r.try_xtile = ((flags & LHPC_PLAN_FORCE_XTILE) || (nolocal && !o.spmv_no_xtile)) && s.n_rows > 0;
+  r.part = xtile_partition_policy(s.n_rows, s.n_cols, s.nnz, s.elem_bytes, s.n_splits, o);
+  r.try_xslice = ((flags & LHPC_PLAN_FORCE_XSLICE) || nolocal) && s.nnz > 0;
+  // Off those paths ADAPTIVE (nnz-balanced blocks, coalesced col/val stream,
+  // LDS row sums) is the default: measured equal or faster than ROWGROUP on
+  // uniform rows of 3-40 nnz (within 4% at 8 and 24), and 1.26-1.5× faster on
+  // C1 and the 2-D Laplacians (tools/explore_rowlen.py).
+  // ROWGROUP stays selectable (FORCE_ROWGROUP).
+  const bool adaptive = !(flags & LHPC_PLAN_FORCE_ROWGROUP) || (flags & LHPC_PLAN_FORCE_ADAPTIVE);
+  if (!adaptive) {
+    r.csr_kernel = LHPC_KERNEL_ROWGROUP;
+    const double mean = s.n_rows ? static_cast<double>(s.nnz) / static_cast<double>(s.n_rows) : 0;
+    int L = 4;
+    while (L < 64 && L < mean) L <<= 1;
+    r.L = L;
+    r.R = L == 4 ? 1 : L <= 16 ? 4 : L == 32 ? 2 : 1;
+    if (o.rowgroup_lanes > 0 || o.rowgroup_rows > 0) {
+      // the (L, R) shapes lhpc_spmv_csr.hip instantiates
+      static const int kShapes[] = {101, 201, 202, 401, 402, 404, 802, 804, 1601, 1602, 1604, 1608, 3201, 3202, 6401};
+      const int want = o.rowgroup_lanes * 100 + o.rowgroup_rows;
+      if (std::find(std::begin(kShapes), std::end(kShapes), want) == std::end(kShapes))
+        r.csr_status = LHPC_ERR_INVALID_ARG;
+      r.L = o.rowgroup_lanes;
+      r.R = o.rowgroup_rows;
+    }
+  }
+  // SELL for short rows (≤ kSellMaxW nonzeros) whose padded slices stream no
+  // more bytes than CSR + row_ptr (the builder's rule): bit-identical to
+  // ADAPTIVE, no row_ptr stream, LDS or barrier (the CG Laplacian: DESIGN.md §4)
+  r.force_sell = (flags & LHPC_PLAN_FORCE_SELL) != 0;
+  r.try_sell = adaptive && (r.force_sell || (auto_ok && !o.spmv_no_sell)) && s.max_row_len <= kSellMaxW && s.n_rows > 0;
   return r;
 }
 

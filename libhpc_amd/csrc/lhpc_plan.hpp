@@ -136,8 +136,8 @@ int build_xtile(const void *row_ptr, int rp_bits, const int32_t *col, int64_t n_
 
 // The decisions of an XTILE plan build, as pure functions of the shape and
 // the options (no HIP call, no environment), so that a host test can put the
-// full-size shapes to them (tests/cpp/asan_plan.cpp).  lhpc_spmv.hip asks
-// xtile_partition_policy, build_t of lhpc_spmv_xtile.hip the other two.
+// full-size shapes to them (tests/cpp/asan_plan.cpp).  spmv_family_policy
+// asks xtile_partition_policy, build_t of lhpc_spmv_xtile.hip the other two.
 //
 // One tile of x fills a gather workgroup's LDS: 160 KB of T
 constexpr int64_t xtile_capacity(size_t elem_bytes) { return 160 * 1024 / static_cast<int64_t>(elem_bytes); }
@@ -155,6 +155,33 @@ struct XtilePartition {
 };
 XtilePartition xtile_partition_policy(int64_t n_rows, int64_t n_cols, int64_t nnz, size_t elem_bytes, int n_splits,
                                       const lhpc_options &o);
+
+// Which kernel family a matrix gets (lhpc_spmv.hip build_single), decided
+// once for host and device input alike, as a pure function like the ones
+// above.  The stages are attempted in the fixed order XTILE → XSLICE → SELL →
+// CSR; a stage that answers LHPC_ERR_UNSUPPORTED hands over to the next one.
+constexpr int kSellMaxW = 8;  // SELL: nonzeros per row at most (ADAPTIVE's 2048 / 256)
+// Is the locality sample (distinct 128-B x lines per nonzero) needed: no
+// family is forced and x outgrows one XCD's 4 MB L2 (> 8.0e6 bytes)
+bool spmv_wants_locality(int64_t n_cols, size_t elem_bytes, unsigned flags);
+struct SpmvShape {
+  int64_t n_rows = 0, n_cols = 0, nnz = 0;
+  size_t elem_bytes = 4;
+  int n_splits = 0;            // user row splits
+  int64_t max_row_len = 0;
+  double lines_per_nnz = 1.0;  // the sample; read only when spmv_wants_locality
+};
+struct SpmvFamilyPolicy {
+  bool try_xtile = false, try_xslice = false, try_sell = false;
+  bool force_sell = false;  // no CSR plan after SELL: LHPC_ERR_UNSUPPORTED instead
+  XtilePartition part;      // how try_xtile builds
+  // the CSR stage: ADAPTIVE, or ROWGROUP with L lanes per row and R rows per
+  // group; csr_status: what the stage returns instead of a plan (a
+  // rowgroup_lanes / rowgroup_rows pair lhpc_spmv_csr.hip does not instantiate)
+  int csr_kernel = LHPC_KERNEL_ADAPTIVE, L = 16, R = 4;
+  int csr_status = LHPC_OK;
+};
+SpmvFamilyPolicy spmv_family_policy(const SpmvShape &s, unsigned flags, const lhpc_options &o);
 
 // tile width: the capacity, narrowed for fp32 to a whole multiple of the CUs
 // when that adds ≤ 10% tiles; narrow: −1 by that rule, 0 / 1 override it

@@ -468,15 +468,8 @@ int plan_build(lhpc_spmm_plan *p, const void *row_ptr, int bits, const int32_t *
     LHPC_HIP_TRY(hipMemcpy(p->d_col, col_idx, nnz * 4, kind));
     LHPC_HIP_TRY(hipMemcpy(p->d_val, val, nnz * tsz, kind));
   }
-  const RowPtrView rp{rp_host, bits};
-  const std::vector<int64_t> b = csr_build_blocks(rp, p->n_rows, p->n_long);
-  p->n_blocks = static_cast<int64_t>(b.size()) - 1;
+  const std::vector<int64_t> bp = csr_block_table(RowPtrView{rp_host, bits}, p->n_rows, p->n_blocks, p->n_long);
   if (p->n_blocks > INT32_MAX) return LHPC_ERR_UNSUPPORTED;  // gridDim.x
-  std::vector<int64_t> bp(2 * b.size());
-  for (size_t i = 0; i < b.size(); ++i) {
-    bp[2 * i] = b[i];
-    bp[2 * i + 1] = rp[b[i]];
-  }
   LHPC_TRY(dmalloc(reinterpret_cast<void **>(&p->d_blocks), bp.size() * 8, p->bytes));
   LHPC_HIP_TRY(hipMemcpy(p->d_blocks, bp.data(), bp.size() * 8, hipMemcpyHostToDevice));
   return LHPC_OK;

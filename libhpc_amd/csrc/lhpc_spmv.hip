@@ -1,6 +1,9 @@
 // lhpc_spmv.hip — CSR SpMV y = A·x for gfx950 (MI355X), behind include/lhpc.h:
-// plan creation (validation, kernel selection, the family builders) and the
-// C ABI.  The kernels live in lhpc_spmv_{csr,xslice,xtile}.hip
+// plan creation and the C ABI.  Creation is one flow for host and device
+// input (plan_create_impl): checks, source set-up (validation), row
+// statistics and the locality sample, then the family stages XTILE → XSLICE
+// → SELL → CSR that lhpc_plan.hpp spmv_family_policy selects (build_single).
+// The kernels and the family builders live in lhpc_spmv_{csr,xslice,xtile}.hip
 // (lhpc_spmv_impl.hpp).
 //
 // The reference has no SpMV; the operator is defined
@@ -11,11 +14,10 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <iterator>
+#include <memory>
 #include <new>
 #include <vector>
 
@@ -26,32 +28,34 @@ namespace lhpc {
 namespace {
 
 // Distinct 128-B x lines touched per nonzero, over up to 32 evenly spaced
-// chunks of 8192 consecutive rows (1.0 = no reuse within a chunk).
-// fetch(k0, k1, out): the columns of nonzeros [k0, k1) (host array or a copy
-// from device-resident input)
-template <typename RP, typename Fetch>
-double gather_lines_per_nnz(const RP &rp, Fetch fetch, int64_t n_rows, int64_t n_cols, size_t tsz) {
+// chunks of 8192 consecutive rows (1.0 = no reuse within a chunk).  The
+// columns of a device source are copied to the host chunk by chunk.
+double gather_lines_per_nnz(const CsrSource &src, int64_t n_rows, int64_t n_cols, size_t tsz) {
   constexpr int64_t kChunk = 8192, kSamples = 32;
   const int shift = tsz == 8 ? 4 : 5;  // 16 doubles / 32 floats per line
   const int64_t chunks = (n_rows + kChunk - 1) / kChunk;
   const int64_t step = std::max<int64_t>(1, chunks / kSamples);
   int64_t lines = 0, nz = 0;
-  std::vector<int32_t> buf;
+  std::vector<int32_t> copy;
   // distinct lines per sample with a bitmap over x's lines (set, count, then
   // clear what was set): O(nonzeros) where a sort + unique cost ≈ 0.2 s for C2
   std::vector<uint64_t> seen(static_cast<size_t>(((n_cols >> shift) + 64) / 64), 0);
   for (int64_t c = 0; c < chunks; c += step) {
     const int64_t r0 = c * kChunk, r1 = std::min(n_rows, r0 + kChunk);
-    const int64_t k0 = rp[r0], k1 = rp[r1];
-    buf.resize(static_cast<size_t>(k1 - k0));
-    if (k1 > k0 && fetch(k0, k1, buf.data()) != LHPC_OK) return 1.0;
-    for (const int32_t v : buf) {
-      const uint64_t l = static_cast<uint64_t>(v) >> shift, bit = uint64_t{1} << (l & 63);
+    const int64_t k0 = src.rp[r0], k1 = src.rp[r1];
+    const int32_t *col = src.col + k0;
+    if (src.d_rp && k1 > k0) {
+      copy.resize(static_cast<size_t>(k1 - k0));
+      if (hipMemcpy(copy.data(), col, copy.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) return 1.0;
+      col = copy.data();
+    }
+    for (int64_t k = 0; k < k1 - k0; ++k) {
+      const uint64_t l = static_cast<uint64_t>(col[k]) >> shift, bit = uint64_t{1} << (l & 63);
       uint64_t &w = seen[static_cast<size_t>(l >> 6)];
       lines += (w & bit) ? 0 : 1;
       w |= bit;
     }
-    for (const int32_t v : buf) seen[static_cast<size_t>((static_cast<uint64_t>(v) >> shift) >> 6)] = 0;
+    for (int64_t k = 0; k < k1 - k0; ++k) seen[static_cast<size_t>((static_cast<uint64_t>(col[k]) >> shift) >> 6)] = 0;
     nz += k1 - k0;
   }
   return nz ? static_cast<double>(lines) / static_cast<double>(nz) : 1.0;
@@ -75,7 +79,7 @@ __global__ void k_validate_device_csr(const void *rp, int bits, const int32_t *c
   if (bad) atomicOr(flag, bad);
 }
 
-// XTILE column blocks from device-resident CSR (build_parts with d_rp):
+// XTILE column blocks from device-resident CSR (build_parts, device source):
 // rows [r0, r0 + nr) restricted to columns [c0, c1), rebased — the device
 // twin of lhpc_plan.cpp csr_column_block (count per row, host scan, scatter)
 __device__ __forceinline__ int64_t rp_dev(const void *rp, int bits, int64_t i) {
@@ -162,6 +166,72 @@ int launch(const lhpc_spmv_plan *p, const void *x, void *y, hipStream_t s) {
   return csr_launch(p, x, y, s);
 }
 
+// ------------------------------------------------------------ plan creation
+// A plan under construction is destroyed with whatever it owns unless
+// creation succeeds and releases it into *out.
+struct PlanDeleter {
+  void operator()(lhpc_spmv_plan *p) const { lhpc_spmv_plan_destroy(p); }
+};
+using PlanPtr = std::unique_ptr<lhpc_spmv_plan, PlanDeleter>;
+
+// nullptr: no memory
+lhpc_spmv_plan *new_plan(const lhpc_options &o, int dtype, int device, int64_t n_rows, int64_t n_cols, int64_t nnz) {
+  auto *p = new (std::nothrow) lhpc_spmv_plan();
+  if (!p) return nullptr;
+  p->opt = o;
+  p->dtype = dtype;
+  p->device = device;
+  p->n_rows = n_rows;
+  p->n_cols = n_cols;
+  p->nnz = nnz;
+  return p;
+}
+
+// a refused XTILE build leaves no parts behind
+void reset_parts(lhpc_spmv_plan *p) {
+  for (auto *q : p->parts) lhpc_spmv_plan_destroy(q);
+  p->parts.clear();
+  p->part_row.clear();
+  p->part_col.clear();
+  p->bytes = 0;
+}
+
+// Host copies of device-resident input: row_ptr from the start (every
+// decision reads it), col / val once a stage without a GPU builder needs them.
+struct HostCopy {
+  std::vector<unsigned char> rp, val;
+  std::vector<int32_t> col;
+};
+
+// LHPC_PLAN_DEVICE_INPUT: row_ptr / col_idx / val in HBM of the plan's device
+// (e.g. straight from lhpc_coo_to_csr on the device), validated on the GPU;
+// row_ptr (n_rows + 1 words) comes back to the host
+int device_source(CsrSource &src, HostCopy &host, int64_t n_rows, int64_t n_cols, int64_t nnz) {
+  RocTxRange rx("lhpc_spmv_plan_create: device input");
+  // the arrays may still be in flight on any stream of the caller (plan
+  // creation is synchronous anyway)
+  LHPC_HIP_TRY(hipDeviceSynchronize());
+  LHPC_TRY(validate_csr_device(src.rp.p, src.rp.bits, src.col, n_rows, n_cols, nnz));
+  host.rp.resize(static_cast<size_t>(n_rows + 1) * (src.rp.bits / 8));
+  LHPC_HIP_TRY(hipMemcpy(host.rp.data(), src.rp.p, host.rp.size(), hipMemcpyDeviceToHost));
+  src.d_rp = src.rp.p;
+  src.rp.p = host.rp.data();
+  return LHPC_OK;
+}
+
+// a stage without a GPU builder: a device source becomes a host source, once
+int to_host(CsrSource &src, HostCopy &host, int64_t nnz, size_t tsz) {
+  if (!src.d_rp) return LHPC_OK;
+  host.col.resize(static_cast<size_t>(nnz));
+  host.val.resize(static_cast<size_t>(nnz) * tsz);
+  if (nnz) {
+    LHPC_HIP_TRY(hipMemcpy(host.col.data(), src.col, host.col.size() * 4, hipMemcpyDeviceToHost));
+    LHPC_HIP_TRY(hipMemcpy(host.val.data(), src.val, host.val.size(), hipMemcpyDeviceToHost));
+  }
+  src = CsrSource{src.rp, host.col.data(), host.val.data(), nullptr};
+  return LHPC_OK;
+}
+
 // XTILE row parts: the tile stream of one plan is addressed with int32
 // offsets (nnz + 8 padding entries per tile < 2^31, lhpc_plan.cpp
 // build_xtile).  A larger matrix (n ≳ 143M rows at 15 nonzeros per row) is
@@ -171,10 +241,10 @@ int launch(const lhpc_spmv_plan *p, const void *x, void *y, hipStream_t s) {
 // B > 1 column blocks every row part is further cut by column (lhpc_plan.cpp
 // xtile_partition_policy).
 // LHPC_ERR_UNSUPPORTED when some single row exceeds the cap.
-// d_rp non-null: device input (col_idx / val and d_rp in HBM, rp a host copy
-// of row_ptr): every part's layout is built on the GPU (xtile_build_device).
-int build_parts(lhpc_spmv_plan *p, RowPtrView rp, const int32_t *col_idx, const void *val, size_t tsz,
-                int64_t cap, int B, const void *d_rp = nullptr) {
+// A device source has every part's column block cut and layout built on the GPU.
+int build_parts(lhpc_spmv_plan *p, const CsrSource &src, int64_t cap, int B) {
+  const RowPtrView rp = src.rp;
+  const size_t tsz = p->dtype == LHPC_F32 ? 4 : 8;
   const int64_t n_rows = p->n_rows;
   int64_t n_parts = std::max<int64_t>(1, (p->nnz + cap - 1) / cap);
   std::vector<int64_t> cuts;
@@ -193,25 +263,21 @@ int build_parts(lhpc_spmv_plan *p, RowPtrView rp, const int32_t *col_idx, const 
   // column block bounds, 64-column aligned (x + bound stays 256-B aligned)
   std::vector<int64_t> cb(static_cast<size_t>(B) + 1, p->n_cols);
   for (int b = 0; b < B; ++b) cb[b] = p->n_cols * b / B / 64 * 64;
-  auto add = [&](int64_t r0, int64_t r1, int64_t c0, int64_t c1, RowPtrView lrp, const int32_t *lc, const void *lv,
-                 int64_t lnnz, int acc) -> int {
-    auto *q = new (std::nothrow) lhpc_spmv_plan();
+  std::vector<int64_t> lrp;  // the part's row offsets, rebased
+  // the part's col / val live where the source's do (xtile_build reads only
+  // whether d_rp is set)
+  auto add = [&](int64_t r0, int64_t r1, int64_t c0, int64_t c1, const int32_t *lc, const void *lv, int64_t lnnz,
+                 int acc) -> int {
+    auto *q = new_plan(p->opt, p->dtype, p->device, r1 - r0, c1 - c0, lnnz);
     if (!q) return LHPC_ERR_ALLOC;
     p->parts.push_back(q);
     p->part_row.push_back(r0);
     p->part_col.push_back(c0);
-    q->opt = p->opt;
-    q->dtype = p->dtype;
-    q->device = p->device;
-    q->n_rows = r1 - r0;
-    q->n_cols = c1 - c0;
-    q->nnz = lnnz;
     q->xt_acc = acc;
-    LHPC_TRY(d_rp ? xtile_build_device(q, lrp, lc, lv, tsz) : xtile_build(q, lrp, lc, lv, tsz));
+    LHPC_TRY(xtile_build(q, CsrSource{RowPtrView{lrp.data(), 64}, lc, lv, src.d_rp}));
     p->bytes += q->bytes;
     return LHPC_OK;
   };
-  std::vector<int64_t> lrp;
   std::vector<int32_t> lcol;
   std::vector<unsigned char> lval;
   for (int64_t i = 0; i < n_parts; ++i) {
@@ -221,13 +287,13 @@ int build_parts(lhpc_spmv_plan *p, RowPtrView rp, const int32_t *col_idx, const 
     if (B == 1 || rp[r1] == e0) {
       lrp.resize(static_cast<size_t>(r1 - r0 + 1));
       for (int64_t r = r0; r <= r1; ++r) lrp[static_cast<size_t>(r - r0)] = rp[r] - e0;
-      LHPC_TRY(add(r0, r1, 0, p->n_cols, RowPtrView{lrp.data(), 64}, col_idx + e0,
-                   static_cast<const unsigned char *>(val) + e0 * static_cast<int64_t>(tsz), rp[r1] - e0, 0));
+      LHPC_TRY(add(r0, r1, 0, p->n_cols, src.col + e0,
+                   static_cast<const unsigned char *>(src.val) + e0 * static_cast<int64_t>(tsz), rp[r1] - e0, 0));
       continue;
     }
     bool first = true;  // the first non-empty block stores every row of the part
     for (int b = 0; b < B; ++b) {
-      if (d_rp) {
+      if (src.d_rp) {
         struct Tmp {
           void *c = nullptr, *v = nullptr;
           ~Tmp() {
@@ -235,16 +301,15 @@ int build_parts(lhpc_spmv_plan *p, RowPtrView rp, const int32_t *col_idx, const 
             if (v) (void)hipFree(v);
           }
         } t;
-        LHPC_TRY(colblock_device(d_rp, rp.bits, col_idx, val, tsz, r0, r1, cb[b], cb[b + 1], lrp, &t.c, &t.v));
+        LHPC_TRY(colblock_device(src.d_rp, rp.bits, src.col, src.val, tsz, r0, r1, cb[b], cb[b + 1], lrp, &t.c, &t.v));
         const int64_t m = lrp.back();
         if (m == 0) continue;  // adds nothing
-        LHPC_TRY(add(r0, r1, cb[b], cb[b + 1], RowPtrView{lrp.data(), 64}, static_cast<const int32_t *>(t.c), t.v, m,
-                     first ? 0 : 1));
+        LHPC_TRY(add(r0, r1, cb[b], cb[b + 1], static_cast<const int32_t *>(t.c), t.v, m, first ? 0 : 1));
       } else {
-        csr_column_block(rp.p, rp.bits, col_idx, val, tsz, r0, r1, cb[b], cb[b + 1], lrp, lcol, lval);
+        csr_column_block(rp.p, rp.bits, src.col, src.val, tsz, r0, r1, cb[b], cb[b + 1], lrp, lcol, lval);
         if (lcol.empty()) continue;  // adds nothing
-        LHPC_TRY(add(r0, r1, cb[b], cb[b + 1], RowPtrView{lrp.data(), 64}, lcol.data(), lval.data(),
-                     static_cast<int64_t>(lcol.size()), first ? 0 : 1));
+        LHPC_TRY(add(r0, r1, cb[b], cb[b + 1], lcol.data(), lval.data(), static_cast<int64_t>(lcol.size()),
+                     first ? 0 : 1));
       }
       first = false;
     }
@@ -256,16 +321,15 @@ int build_parts(lhpc_spmv_plan *p, RowPtrView rp, const int32_t *col_idx, const 
   return LHPC_OK;
 }
 
-int plan_create_device_input(lhpc_spmv_plan **out, int dtype, int64_t n_rows, int64_t n_cols, int64_t nnz,
-                             const void *row_ptr, int row_ptr_bits, const int32_t *col_idx, const void *val,
-                             const int *device_ids, int n_devices, unsigned flags, int n_splits,
-                             const int64_t *split_rows, const lhpc_options *opts);
+// one plan, or row parts × column blocks (lhpc_plan.hpp xtile_partition_policy)
+int xtile_build_whole(lhpc_spmv_plan *p, const CsrSource &src, const XtilePartition &pp) {
+  return pp.parts ? build_parts(p, src, pp.cap, pp.col_blocks) : xtile_build(p, src);
+}
 
-// host A → HBM copies → the device layout build (xtile_build_device /
-// build_parts on the device); LHPC_ERR_UNSUPPORTED when the device build
-// does not apply (aligned segments) or the copies do not fit in HBM
-int xtile_build_uploaded(lhpc_spmv_plan *p, RowPtrView rp, const void *row_ptr, const int32_t *col_idx,
-                         const void *val, size_t tsz, bool parts, int64_t cap, int B) {
+// host A → HBM copies → the device layout build; LHPC_ERR_UNSUPPORTED when
+// the device build does not apply (aligned segments) or the copies do not fit
+// in HBM
+int xtile_build_uploaded(lhpc_spmv_plan *p, const CsrSource &src, const XtilePartition &pp) {
   if (p->opt.xtile_host_build == 1 || p->opt.xtile_align == LHPC_XTILE_ALIGN_UNITS || p->nnz == 0)
     return LHPC_ERR_UNSUPPORTED;
   struct Tmp {
@@ -274,20 +338,112 @@ int xtile_build_uploaded(lhpc_spmv_plan *p, RowPtrView rp, const void *row_ptr, 
       if (a) (void)hipFree(a);
     }
   } d_rp, d_col, d_val;
-  const size_t rpb = static_cast<size_t>(p->n_rows + 1) * (rp.bits / 8);
+  const size_t tsz = p->dtype == LHPC_F32 ? 4 : 8;
+  const size_t rpb = static_cast<size_t>(p->n_rows + 1) * (src.rp.bits / 8);
   const size_t nnz = static_cast<size_t>(p->nnz);
-  if (hipMalloc(&d_rp.a, rpb) != hipSuccess || hipMalloc(&d_col.a, std::max<size_t>(nnz, 1) * 4) != hipSuccess ||
-      hipMalloc(&d_val.a, std::max<size_t>(nnz, 1) * tsz) != hipSuccess) {
+  if (hipMalloc(&d_rp.a, rpb) != hipSuccess || hipMalloc(&d_col.a, nnz * 4) != hipSuccess ||
+      hipMalloc(&d_val.a, nnz * tsz) != hipSuccess) {
     (void)hipGetLastError();
     return LHPC_ERR_UNSUPPORTED;
   }
-  LHPC_HIP_TRY(hipMemcpy(d_rp.a, row_ptr, rpb, hipMemcpyHostToDevice));
-  if (nnz) {
-    LHPC_HIP_TRY(hipMemcpy(d_col.a, col_idx, nnz * 4, hipMemcpyHostToDevice));
-    LHPC_HIP_TRY(hipMemcpy(d_val.a, val, nnz * tsz, hipMemcpyHostToDevice));
+  LHPC_HIP_TRY(hipMemcpy(d_rp.a, src.rp.p, rpb, hipMemcpyHostToDevice));
+  LHPC_HIP_TRY(hipMemcpy(d_col.a, src.col, nnz * 4, hipMemcpyHostToDevice));
+  LHPC_HIP_TRY(hipMemcpy(d_val.a, src.val, nnz * tsz, hipMemcpyHostToDevice));
+  return xtile_build_whole(p, CsrSource{src.rp, static_cast<const int32_t *>(d_col.a), d_val.a, d_rp.a}, pp);
+}
+
+// The XTILE stage.  The layout is built on the GPU: from a device source as
+// it is, from host arrays through uploaded copies (byte-identical to the host
+// build, DESIGN.md §4 device input; C2 0.57 → ≈ 0.15 s).  The host build takes
+// over when the GPU build refuses (aligned segments, no memory).  The GPU
+// build makes the host build's own refusals (xtile_plan_chunks: tiles, int32
+// stream offsets), so a device source needs no guard in front of it: what
+// neither can hold ends as LHPC_ERR_UNSUPPORTED, for XSLICE or a CSR kernel.
+int xtile_stage(lhpc_spmv_plan *p, CsrSource &src, HostCopy &host, const XtilePartition &pp) {
+  const size_t tsz = p->dtype == LHPC_F32 ? 4 : 8;
+  const std::vector<int64_t> splits_in = p->split_rows;  // a build may add cache-range cuts
+  int st = src.d_rp ? xtile_build_whole(p, src, pp) : xtile_build_uploaded(p, src, pp);
+  if (st == LHPC_ERR_UNSUPPORTED) {
+    reset_parts(p);
+    p->split_rows = splits_in;
+    LHPC_TRY(to_host(src, host, p->nnz, tsz));
+    st = xtile_build_whole(p, src, pp);
   }
-  const int32_t *dc = static_cast<const int32_t *>(d_col.a);
-  return parts ? build_parts(p, rp, dc, d_val.a, tsz, cap, B, d_rp.a) : xtile_build_device(p, rp, dc, d_val.a, tsz);
+  if (st == LHPC_ERR_UNSUPPORTED) reset_parts(p);
+  return st;
+}
+
+// The CSR stage: ROWGROUP / ADAPTIVE keep the caller's CSR — row_ptr (int32
+// offsets whenever they fit: 4 B/row less HBM traffic), col, val — and
+// ADAPTIVE its block table
+int csr_upload(lhpc_spmv_plan *p, const CsrSource &src, size_t tsz) {
+  const size_t nnz = static_cast<size_t>(p->nnz);
+  p->rp64 = p->nnz > INT32_MAX ? 1 : 0;
+  const size_t rp_bytes = static_cast<size_t>(p->n_rows + 1) * (p->rp64 ? 8 : 4);
+  LHPC_TRY(dmalloc(&p->d_row_ptr, rp_bytes, p->bytes));
+  LHPC_TRY(dmalloc(reinterpret_cast<void **>(&p->d_col), nnz * 4, p->bytes));
+  LHPC_TRY(dmalloc(&p->d_val, nnz * tsz, p->bytes));
+  if (p->rp64 == (src.rp.bits == 64 ? 1 : 0)) {
+    LHPC_HIP_TRY(hipMemcpy(p->d_row_ptr, src.rp.p, rp_bytes, hipMemcpyHostToDevice));
+  } else {  // row_ptr in the device width
+    std::vector<int32_t> tmp(static_cast<size_t>(p->n_rows + 1));
+    for (int64_t i = 0; i <= p->n_rows; ++i) tmp[static_cast<size_t>(i)] = static_cast<int32_t>(src.rp[i]);
+    LHPC_HIP_TRY(hipMemcpy(p->d_row_ptr, tmp.data(), rp_bytes, hipMemcpyHostToDevice));
+  }
+  if (nnz) {
+    LHPC_HIP_TRY(hipMemcpy(p->d_col, src.col, nnz * 4, hipMemcpyHostToDevice));
+    LHPC_HIP_TRY(hipMemcpy(p->d_val, src.val, nnz * tsz, hipMemcpyHostToDevice));
+  }
+  if (p->kernel != LHPC_KERNEL_ADAPTIVE) return LHPC_OK;
+  const std::vector<int64_t> bp = csr_block_table(src.rp, p->n_rows, p->n_blocks, p->n_long);
+  LHPC_TRY(dmalloc(reinterpret_cast<void **>(&p->d_blocks), bp.size() * 8, p->bytes));
+  LHPC_HIP_TRY(hipMemcpy(p->d_blocks, bp.data(), bp.size() * 8, hipMemcpyHostToDevice));
+  return LHPC_OK;
+}
+
+// A single-device plan: row statistics, the locality sample if the policy
+// wants it, then the family stages in spmv_family_policy's order.  A stage
+// that answers LHPC_ERR_UNSUPPORTED leaves the plan to the next one.  A device
+// source stays on the device for the stages with a GPU builder (XTILE, SELL);
+// the first stage without one copies it to the host (to_host).
+int build_single(lhpc_spmv_plan *p, CsrSource &src, HostCopy &host, unsigned flags, int n_splits) {
+  const size_t tsz = p->dtype == LHPC_F32 ? 4 : 8;
+  SpmvShape sh;
+  sh.n_rows = p->n_rows;
+  sh.n_cols = p->n_cols;
+  sh.nnz = p->nnz;
+  sh.elem_bytes = tsz;
+  sh.n_splits = n_splits;
+  for (int64_t i = 0; i < p->n_rows; ++i) sh.max_row_len = std::max(sh.max_row_len, src.rp[i + 1] - src.rp[i]);
+  if (spmv_wants_locality(p->n_cols, tsz, flags)) sh.lines_per_nnz = gather_lines_per_nnz(src, p->n_rows, p->n_cols, tsz);
+  const SpmvFamilyPolicy pol = spmv_family_policy(sh, flags, p->opt);
+
+  int st = LHPC_ERR_UNSUPPORTED;
+  if (pol.try_xtile) st = xtile_stage(p, src, host, pol.part);
+  if (st == LHPC_ERR_UNSUPPORTED && pol.try_xslice) {
+    LHPC_TRY(to_host(src, host, p->nnz, tsz));
+    st = xslice_build(p, src.rp, src.col, src.val, tsz, flags);
+  }
+  if (st == LHPC_ERR_UNSUPPORTED && pol.try_sell) st = sell_build(p, src, tsz, pol.force_sell);
+  if (st != LHPC_ERR_UNSUPPORTED) return st;
+  LHPC_TRY(pol.csr_status);
+  if (pol.force_sell) return LHPC_ERR_UNSUPPORTED;  // a row longer than kSellMaxW (or no rows)
+  p->kernel = pol.csr_kernel;
+  p->L = pol.L;
+  p->R = pol.R;
+  LHPC_TRY(to_host(src, host, p->nnz, tsz));
+  return csr_upload(p, src, tsz);
+}
+
+// the plan's device: device_ids[0] or the current one, and a gfx950
+int pick_device(const int *device_ids, int n_devices, int &dev) {
+  if (device_ids && n_devices >= 1) {
+    dev = device_ids[0];
+    LHPC_HIP_TRY(hipSetDevice(dev));
+  } else {
+    LHPC_HIP_TRY(hipGetDevice(&dev));
+  }
+  return is_gfx950(dev) ? LHPC_OK : LHPC_ERR_NO_DEVICE;
 }
 
 int plan_create_impl(lhpc_spmv_plan **out, int dtype, int64_t n_rows, int64_t n_cols, int64_t nnz,
@@ -303,353 +459,43 @@ int plan_create_impl(lhpc_spmv_plan **out, int dtype, int64_t n_rows, int64_t n_
     return LHPC_ERR_INVALID_ARG;
   if (n_devices < 0 || (n_devices > 1 && !device_ids)) return LHPC_ERR_INVALID_ARG;
   if (row_ptr_bits == 32 && nnz > INT32_MAX) return LHPC_ERR_INVALID_ARG;
-  if (flags & LHPC_PLAN_DEVICE_INPUT)
-    return plan_create_device_input(out, dtype, n_rows, n_cols, nnz, row_ptr, row_ptr_bits, col_idx, val, device_ids,
-                                    n_devices, flags, n_splits, split_rows, opts);
-
-  const RowPtrView rp{row_ptr, row_ptr_bits};
-  // always: every layout pass below indexes host arrays by row_ptr / col_idx,
-  // and every kernel indexes x by col_idx (LHPC_PLAN_VALIDATE is implied)
-  LHPC_TRY(validate_csr(row_ptr, row_ptr_bits, col_idx, n_rows, n_cols, nnz));
-
   // several devices driven by this one host thread: one local
   // plan, stream, comm stream (and RCCL comm) per device (lhpc_multi.hip)
-  if (n_devices > 1 || (o.multi_force && n_devices == 1 && device_ids)) {
+  const bool multi = n_devices > 1 || (o.multi_force && n_devices == 1 && device_ids);
+  const bool device_input = (flags & LHPC_PLAN_DEVICE_INPUT) != 0;
+  flags &= ~static_cast<unsigned>(LHPC_PLAN_DEVICE_INPUT);  // from here on src says where A lives
+
+  CsrSource src{RowPtrView{row_ptr, row_ptr_bits}, col_idx, val, nullptr};
+  HostCopy host;
+  int dev = 0;
+  if (device_input) {
+    LHPC_TRY(pick_device(device_ids, n_devices, dev));  // where the arrays are
+    LHPC_TRY(device_source(src, host, n_rows, n_cols, nnz));
+  } else {
+    // always: every layout pass indexes host arrays by row_ptr / col_idx, and
+    // every kernel indexes x by col_idx (LHPC_PLAN_VALIDATE is implied)
+    LHPC_TRY(validate_csr(row_ptr, row_ptr_bits, col_idx, n_rows, n_cols, nnz));
+  }
+  if (multi) {  // built from host arrays; picks its devices itself
     if (n_splits > 0) return LHPC_ERR_UNSUPPORTED;
-    auto *p = new (std::nothrow) lhpc_spmv_plan();
+    LHPC_TRY(to_host(src, host, nnz, dtype == LHPC_F32 ? 4 : 8));
+    PlanPtr p(new_plan(o, dtype, 0, n_rows, n_cols, nnz));
     if (!p) return LHPC_ERR_ALLOC;
-    p->opt = o;
-    p->dtype = dtype;
-    p->n_rows = n_rows;
-    p->n_cols = n_cols;
-    p->nnz = nnz;
-    const int st = multi_create(p, rp, col_idx, val, device_ids, n_devices, flags);
-    if (st != LHPC_OK) {
-      lhpc_spmv_plan_destroy(p);
-      return st;
-    }
-    *out = p;
+    LHPC_TRY(multi_create(p.get(), src.rp, src.col, src.val, device_ids, n_devices, flags));
+    *out = p.release();
     return LHPC_OK;
   }
+  if (!device_input) LHPC_TRY(pick_device(device_ids, n_devices, dev));
 
-  int dev = 0;
-  if (device_ids && n_devices == 1) {
-    dev = device_ids[0];
-    LHPC_HIP_TRY(hipSetDevice(dev));
-  } else {
-    LHPC_HIP_TRY(hipGetDevice(&dev));
-  }
-  if (!is_gfx950(dev)) return LHPC_ERR_NO_DEVICE;
-
-  auto *p = new (std::nothrow) lhpc_spmv_plan();
+  PlanPtr p(new_plan(o, dtype, dev, n_rows, n_cols, nnz));
   if (!p) return LHPC_ERR_ALLOC;
-  p->opt = o;
   if (n_splits > 0) p->split_rows.assign(split_rows, split_rows + n_splits);
-  p->dtype = dtype;
-  p->device = dev;
-  p->n_rows = n_rows;
-  p->n_cols = n_cols;
-  p->nnz = nnz;
-  // int32 offsets whenever they fit: 4 B/row less HBM traffic
-  p->rp64 = nnz > INT32_MAX ? 1 : 0;
-  const size_t tsz = dtype == LHPC_F32 ? 4 : 8;
-
-  // ---- kernel selection from row-length statistics
-  int64_t maxlen = 0;
-  double sum2 = 0;
-  for (int64_t i = 0; i < n_rows; ++i) {
-    const int64_t l = rp[i + 1] - rp[i];
-    maxlen = std::max(maxlen, l);
-    sum2 += static_cast<double>(l) * static_cast<double>(l);
-  }
-  const double mean = n_rows ? static_cast<double>(nnz) / static_cast<double>(n_rows) : 0;
-  const double var = n_rows ? sum2 / static_cast<double>(n_rows) - mean * mean : 0;
-  const double cv = mean > 0 ? std::sqrt(std::max(var, 0.0)) / mean : 0;
-  // Off the XSLICE path ADAPTIVE (nnz-balanced blocks, coalesced col/val stream,
-  // LDS row sums) is the default: measured equal or faster than ROWGROUP on
-  // uniform rows of 3-40 nnz (within 4% at 8 and 24), and 1.26-1.5× faster on
-  // C1 and the 2-D Laplacians (tools/explore_rowlen.py).
-  // ROWGROUP stays selectable (FORCE_ROWGROUP); `cv`/`maxlen` are kept for info.
-  (void)cv;
-  bool adaptive = true;
-  if (flags & LHPC_PLAN_FORCE_ROWGROUP) adaptive = false;
-  if (flags & LHPC_PLAN_FORCE_ADAPTIVE) adaptive = true;
-  // XSLICE / XTILE when x outgrows one XCD's 4 MB L2
-  const double x_bytes = static_cast<double>(n_cols) * static_cast<double>(tsz);
-  // ... and only when the gathers have no locality of their own: a banded or
-  // structured matrix (stencil operators, the CG Laplacian) re-reads each x
-  // line from neighbouring rows, which the row-local kernels already serve
-  // from L2, while XSLICE would add S partials per row.  Measure it: distinct
-  // 128-B x lines per nonzero over sampled 8192-row chunks (≈0.8 for C2's
-  // uniform columns, ≈0.03 for a 2-D Laplacian); ≤ 0.25 counts as local.
-  const double locality_thr = o.spmv_locality > 0 ? o.spmv_locality : 0.25;
-  const bool auto_ok = !(flags & (LHPC_PLAN_FORCE_ROWGROUP | LHPC_PLAN_FORCE_ADAPTIVE |
-                                   LHPC_PLAN_FORCE_XSLICE | LHPC_PLAN_FORCE_XTILE | LHPC_PLAN_FORCE_SELL));
-  const bool nolocal =
-      auto_ok && x_bytes > 8.0e6 && gather_lines_per_nnz(
-          rp,
-          [&](int64_t k0, int64_t k1, int32_t *out) {
-            std::memcpy(out, col_idx + k0, static_cast<size_t>(k1 - k0) * 4);
-            return LHPC_OK;
-          },
-          n_rows, n_cols, tsz) > locality_thr;
-  // XTILE (x tiles in LDS) is the default for gathers without locality;
-  // options.spmv_no_xtile selects XSLICE instead.
-  const bool want_xtile = (flags & LHPC_PLAN_FORCE_XTILE) || (nolocal && !o.spmv_no_xtile);
-  if (want_xtile && n_rows > 0) {
-    // row parts and column blocks, or one plan (lhpc_plan.hpp xtile_partition_policy)
-    const XtilePartition pp = xtile_partition_policy(n_rows, n_cols, nnz, tsz, n_splits, o);
-    const int64_t cap = pp.cap;
-    const int B = pp.col_blocks;
-    const bool parts = pp.parts;
-    // the layout is built on the GPU from uploaded copies of A (byte-identical
-    // to the host build, DESIGN.md §4 device input; C2 0.57 → ≈ 0.15 s); the
-    // host build when the device cannot (aligned segments, no memory)
-    const std::vector<int64_t> splits_in = p->split_rows;  // a build may add cache-range cuts
-    int st = xtile_build_uploaded(p, rp, row_ptr, col_idx, val, tsz, parts, cap, B);
-    if (st == LHPC_ERR_UNSUPPORTED) {
-      p->split_rows = splits_in;
-      for (auto *q : p->parts) lhpc_spmv_plan_destroy(q);
-      p->parts.clear();
-      p->part_row.clear();
-      p->part_col.clear();
-      p->bytes = 0;
-      st = parts ? build_parts(p, rp, col_idx, val, tsz, cap, B) : xtile_build(p, rp, col_idx, val, tsz);
-    }
-    if (st == LHPC_OK) {
-      *out = p;
-      return LHPC_OK;
-    }
-    if (st != LHPC_ERR_UNSUPPORTED) {
-      lhpc_spmv_plan_destroy(p);
-      return st;
-    }
-    for (auto *q : p->parts) lhpc_spmv_plan_destroy(q);
-    p->parts.clear();
-    p->part_row.clear();
-    p->part_col.clear();
-    p->bytes = 0;
-    // layout does not fit its index types: XSLICE / CSR kernels below
-  }
-  const bool want_xslice = (flags & LHPC_PLAN_FORCE_XSLICE) || nolocal;
-  if (want_xslice && nnz > 0) {
-    const int st = xslice_build(p, rp, col_idx, val, tsz, flags);
-    if (st == LHPC_OK) {
-      *out = p;
-      return LHPC_OK;
-    }
-    if (st != LHPC_ERR_UNSUPPORTED) {
-      lhpc_spmv_plan_destroy(p);
-      return st;
-    }
-    // some row too long for one slice: fall through to a CSR kernel
-  }
-  if (adaptive) {
-    p->kernel = LHPC_KERNEL_ADAPTIVE;
-  } else {
-    p->kernel = LHPC_KERNEL_ROWGROUP;
-    int L = 4;
-    while (L < 64 && L < mean) L <<= 1;
-    p->L = L;
-    p->R = L <= 16 ? 4 : (L == 32 ? 2 : 1);
-    if (L == 4) p->R = 1;
-  }
-  if (p->kernel == LHPC_KERNEL_ROWGROUP && (o.rowgroup_lanes > 0 || o.rowgroup_rows > 0)) {
-    // the (L, R) shapes lhpc_spmv_csr.hip instantiates
-    static const int kShapes[] = {101, 201, 202, 401, 402, 404, 802, 804, 1601, 1602, 1604, 1608, 3201, 3202, 6401};
-    const int want = o.rowgroup_lanes * 100 + o.rowgroup_rows;
-    if (std::find(std::begin(kShapes), std::end(kShapes), want) == std::end(kShapes)) {
-      lhpc_spmv_plan_destroy(p);
-      return LHPC_ERR_INVALID_ARG;
-    }
-    p->L = o.rowgroup_lanes;
-    p->R = o.rowgroup_rows;
-  }
-
-  // SELL for short rows (≤ 8 nonzeros) whose padded slices stream no more
-  // bytes than CSR + row_ptr: bit-identical to ADAPTIVE, no row_ptr stream,
-  // LDS or barrier (the CG Laplacian: DESIGN.md §4)
-  const bool force_sell = (flags & LHPC_PLAN_FORCE_SELL) != 0;
-  if (p->kernel == LHPC_KERNEL_ADAPTIVE && (force_sell || (auto_ok && !o.spmv_no_sell)) && maxlen <= kSellMaxW &&
-      n_rows > 0) {
-    const int st = sell_build(p, rp, col_idx, val, tsz, force_sell);
-    if (st == LHPC_OK) {
-      *out = p;
-      return LHPC_OK;
-    }
-    if (st != LHPC_ERR_UNSUPPORTED) {
-      lhpc_spmv_plan_destroy(p);
-      return st;
-    }
-  }
-  if (force_sell) {
-    lhpc_spmv_plan_destroy(p);
-    return LHPC_ERR_UNSUPPORTED;  // a row longer than kSellMaxW (or no rows)
-  }
-
-  int st = LHPC_OK;
-  do {
-    const size_t rp_bytes = static_cast<size_t>(n_rows + 1) * (p->rp64 ? 8 : 4);
-    if ((st = dmalloc(&p->d_row_ptr, rp_bytes, p->bytes))) break;
-    if ((st = dmalloc(reinterpret_cast<void **>(&p->d_col), static_cast<size_t>(nnz) * 4,
-                      p->bytes)))
-      break;
-    if ((st = dmalloc(&p->d_val, static_cast<size_t>(nnz) * tsz, p->bytes))) break;
-    // row_ptr in the device width
-    if (p->rp64 == (row_ptr_bits == 64 ? 1 : 0)) {
-      if ((st = static_cast<int>(hipMemcpy(p->d_row_ptr, row_ptr, rp_bytes, hipMemcpyHostToDevice))))
-        break;
-    } else {
-      std::vector<int32_t> tmp(static_cast<size_t>(n_rows + 1));
-      for (int64_t i = 0; i <= n_rows; ++i) tmp[static_cast<size_t>(i)] = static_cast<int32_t>(rp[i]);
-      if ((st = static_cast<int>(hipMemcpy(p->d_row_ptr, tmp.data(), rp_bytes, hipMemcpyHostToDevice))))
-        break;
-    }
-    if (nnz) {
-      if ((st = static_cast<int>(hipMemcpy(p->d_col, col_idx, static_cast<size_t>(nnz) * 4,
-                                           hipMemcpyHostToDevice))))
-        break;
-      if ((st = static_cast<int>(hipMemcpy(p->d_val, val, static_cast<size_t>(nnz) * tsz,
-                                           hipMemcpyHostToDevice))))
-        break;
-    }
-    if (p->kernel == LHPC_KERNEL_ADAPTIVE) {
-      std::vector<int64_t> b = csr_build_blocks(rp, n_rows, p->n_long);
-      p->n_blocks = static_cast<int64_t>(b.size()) - 1;
-      // device table: {first row, its row_ptr} per block boundary, so a block
-      // reads its row and nonzero range with one 32-B load (no dependent
-      // row_ptr round trip)
-      std::vector<int64_t> bp(2 * b.size());
-      for (size_t k = 0; k < b.size(); ++k) {
-        bp[2 * k] = b[k];
-        bp[2 * k + 1] = rp[b[k]];
-      }
-      if ((st = dmalloc(reinterpret_cast<void **>(&p->d_blocks), bp.size() * 8, p->bytes))) break;
-      if ((st = static_cast<int>(hipMemcpy(p->d_blocks, bp.data(), bp.size() * 8, hipMemcpyHostToDevice))))
-        break;
-    }
-  } while (false);
-  if (st != LHPC_OK) {
-    lhpc_spmv_plan_destroy(p);
-    return st;
-  }
-  *out = p;
+  LHPC_TRY(build_single(p.get(), src, host, flags, n_splits));
+  // row ranges exist only in the XTILE tile-stream layout
+  if (n_splits > 0 && (p->kernel != LHPC_KERNEL_XTILE || p->xt_srow.size() != static_cast<size_t>(n_splits) + 2))
+    return LHPC_ERR_UNSUPPORTED;
+  *out = p.release();
   return LHPC_OK;
-}
-// LHPC_PLAN_DEVICE_INPUT: row_ptr / col_idx / val in HBM of the plan's
-// device (e.g. straight from lhpc_coo_to_csr on the device).  Validated on
-// the GPU; row_ptr (n_rows + 1 words) and the 32 locality samples come back
-// to the host, which makes every layout decision.  The XTILE layout — the
-// default for gathers without locality — is then built on the GPU from the
-// device arrays (xtile_build_device: byte-identical to the host build); any
-// other family, aligned segments or several devices copy A to the host and
-// take the host path; row parts and column blocks are built on the GPU too.
-int plan_create_device_input(lhpc_spmv_plan **out, int dtype, int64_t n_rows, int64_t n_cols, int64_t nnz,
-                             const void *row_ptr, int row_ptr_bits, const int32_t *col_idx, const void *val,
-                             const int *device_ids, int n_devices, unsigned flags, int n_splits,
-                             const int64_t *split_rows, const lhpc_options *opts) {
-  RocTxRange rx("lhpc_spmv_plan_create: device input");
-  const lhpc_options o = resolve_options(opts);
-  int dev = 0;
-  if (device_ids && n_devices >= 1) {
-    dev = device_ids[0];
-    LHPC_HIP_TRY(hipSetDevice(dev));
-  } else {
-    LHPC_HIP_TRY(hipGetDevice(&dev));
-  }
-  if (!is_gfx950(dev)) return LHPC_ERR_NO_DEVICE;
-  // the arrays may still be in flight on any stream of the caller (plan
-  // creation is synchronous anyway)
-  LHPC_HIP_TRY(hipDeviceSynchronize());
-  const size_t tsz = dtype == LHPC_F32 ? 4 : 8;
-  LHPC_TRY(validate_csr_device(row_ptr, row_ptr_bits, col_idx, n_rows, n_cols, nnz));
-  const size_t rpb = static_cast<size_t>(n_rows + 1) * (row_ptr_bits / 8);
-  std::vector<unsigned char> hrp(rpb);
-  LHPC_HIP_TRY(hipMemcpy(hrp.data(), row_ptr, rpb, hipMemcpyDeviceToHost));
-  const RowPtrView rp{hrp.data(), row_ptr_bits};
-  // the host path's XTILE decision (plan_create_impl), on the copied row_ptr
-  // and device-fetched locality samples
-  const double x_bytes = static_cast<double>(n_cols) * static_cast<double>(tsz);
-  const double locality_thr = o.spmv_locality > 0 ? o.spmv_locality : 0.25;
-  const bool auto_ok = !(flags & (LHPC_PLAN_FORCE_ROWGROUP | LHPC_PLAN_FORCE_ADAPTIVE | LHPC_PLAN_FORCE_XSLICE |
-                                   LHPC_PLAN_FORCE_XTILE | LHPC_PLAN_FORCE_SELL));
-  // row parts and column blocks as plan_create_impl chooses them; what parts
-  // cannot hold, or one plan cannot (the host path's xtile_build would refuse
-  // it, or build it whole under user splits), is left to the host path
-  const XtilePartition pp = xtile_partition_policy(n_rows, n_cols, nnz, tsz, n_splits, o);
-  const int64_t cap = pp.cap;
-  const int B = pp.col_blocks;
-  const bool parts = pp.parts;
-  const bool single = n_devices <= 1 && !o.multi_force && n_rows > 0 &&
-                      (parts || (nnz <= cap && pp.tiles <= kXtMaxTiles));
-  bool want_xtile = single && (flags & LHPC_PLAN_FORCE_XTILE);
-  // the host path's locality test (plan_create_impl's `nolocal`), on
-  // device-fetched samples: XTILE here, and the SELL decision below
-  bool nolocal = false;
-  if (auto_ok && x_bytes > 8.0e6)
-    nolocal = gather_lines_per_nnz(
-                  rp,
-                  [&](int64_t k0, int64_t k1, int32_t *dst) {
-                    return static_cast<int>(hipMemcpy(dst, col_idx + k0, static_cast<size_t>(k1 - k0) * 4,
-                                                      hipMemcpyDeviceToHost));
-                  },
-                  n_rows, n_cols, tsz) > locality_thr;
-  if (single && auto_ok && !o.spmv_no_xtile && x_bytes > 8.0e6) want_xtile = nolocal;
-  if (want_xtile) {
-    auto *p = new (std::nothrow) lhpc_spmv_plan();
-    if (!p) return LHPC_ERR_ALLOC;
-    p->opt = o;
-    if (n_splits > 0) p->split_rows.assign(split_rows, split_rows + n_splits);
-    p->dtype = dtype;
-    p->device = dev;
-    p->n_rows = n_rows;
-    p->n_cols = n_cols;
-    p->nnz = nnz;
-    const int st = parts ? build_parts(p, rp, col_idx, val, tsz, cap, B, row_ptr)
-                         : xtile_build_device(p, rp, col_idx, val, tsz);
-    if (st == LHPC_OK) {
-      *out = p;
-      return LHPC_OK;
-    }
-    lhpc_spmv_plan_destroy(p);
-    if (st != LHPC_ERR_UNSUPPORTED) return st;
-  }
-  // SELL (short rows with x locality, as plan_create_impl selects it) built
-  // on the GPU from the device arrays; when the padding rule refuses it, the
-  // host path below chooses again (ADAPTIVE)
-  const bool force_sell = (flags & LHPC_PLAN_FORCE_SELL) != 0;
-  if (n_devices <= 1 && !o.multi_force && n_splits == 0 && n_rows > 0 &&
-      (force_sell || (auto_ok && !o.spmv_no_sell && !nolocal))) {
-    int64_t maxlen = 0;
-    for (int64_t i = 0; i < n_rows; ++i) maxlen = std::max<int64_t>(maxlen, rp[i + 1] - rp[i]);
-    if (maxlen <= kSellMaxW) {
-      auto *p = new (std::nothrow) lhpc_spmv_plan();
-      if (!p) return LHPC_ERR_ALLOC;
-      p->opt = o;
-      p->dtype = dtype;
-      p->device = dev;
-      p->n_rows = n_rows;
-      p->n_cols = n_cols;
-      p->nnz = nnz;
-      const int st = sell_build_device(p, rp, row_ptr, col_idx, val, tsz, force_sell);
-      if (st == LHPC_OK) {
-        *out = p;
-        return LHPC_OK;
-      }
-      lhpc_spmv_plan_destroy(p);
-      if (st != LHPC_ERR_UNSUPPORTED) return st;
-    }
-  }
-  // every other case: A to the host, the host path
-  std::vector<int32_t> hcol(static_cast<size_t>(nnz));
-  std::vector<unsigned char> hval(static_cast<size_t>(nnz) * tsz);
-  if (nnz) {
-    LHPC_HIP_TRY(hipMemcpy(hcol.data(), col_idx, static_cast<size_t>(nnz) * 4, hipMemcpyDeviceToHost));
-    LHPC_HIP_TRY(hipMemcpy(hval.data(), val, static_cast<size_t>(nnz) * tsz, hipMemcpyDeviceToHost));
-  }
-  return plan_create_impl(out, dtype, n_rows, n_cols, nnz, hrp.data(), row_ptr_bits, hcol.data(), hval.data(),
-                          device_ids, n_devices, flags & ~static_cast<unsigned>(LHPC_PLAN_DEVICE_INPUT), n_splits,
-                          split_rows, opts);
 }
 
 }  // namespace
@@ -705,16 +551,8 @@ extern "C" int lhpc_spmv_plan_create_opts(lhpc_spmv_plan **out, int dtype, int64
       if (split_rows[i] <= 0 || split_rows[i] >= n_rows || (i > 0 && split_rows[i] <= split_rows[i - 1]))
         return LHPC_ERR_INVALID_ARG;
     RocTxRange rx("lhpc_spmv_plan_create");
-    const int st = plan_create_impl(out, dtype, n_rows, n_cols, nnz, row_ptr, row_ptr_bits, col_idx, val,
-                                    device_ids, n_devices, flags, n_splits, split_rows, opts);
-    if (st != LHPC_OK || n_splits == 0) return st;
-    const lhpc_spmv_plan *p = *out;
-    if (p->kernel != LHPC_KERNEL_XTILE || p->xt_srow.size() != static_cast<size_t>(n_splits) + 2) {
-      lhpc_spmv_plan_destroy(*out);  // ranges exist only in the XTILE tile-stream layout
-      *out = nullptr;
-      return LHPC_ERR_UNSUPPORTED;
-    }
-    return LHPC_OK;
+    return plan_create_impl(out, dtype, n_rows, n_cols, nnz, row_ptr, row_ptr_bits, col_idx, val, device_ids,
+                            n_devices, flags, n_splits, split_rows, opts);
   } LHPC_ABI_CATCH
 }
 

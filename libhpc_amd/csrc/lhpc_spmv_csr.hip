@@ -224,7 +224,7 @@ __device__ __forceinline__ T sell_x(const T *__restrict__ x, int32_t c, int64_t 
 #endif
 }
 
-// Device build of the SELL layout from device CSR (sell_build_device): row i
+// Device build of the SELL layout from device CSR (sell_build, device source): row i
 // (one thread) writes its entries to soff[i / 64] + 64·j + i % 64; padding
 // was set beforehand (col −1, val 0).  V: the value's bit pattern.
 template <typename V>
@@ -528,7 +528,7 @@ int dpart_finish(const lhpc_spmv_plan *p, int64_t n1, double *dot_out, hipStream
 
 // Row blocks for ADAPTIVE: greedy, each block <= kBlockNnz nonzeros and
 // <= kBlock rows, or a single row of any length.
-std::vector<int64_t> csr_build_blocks(RowPtrView rp, int64_t n_rows, int64_t &n_long) {
+static std::vector<int64_t> csr_build_blocks(RowPtrView rp, int64_t n_rows, int64_t &n_long) {
   std::vector<int64_t> b;
   b.reserve(static_cast<size_t>(n_rows / 64 + 2));
   n_long = 0;
@@ -547,6 +547,17 @@ std::vector<int64_t> csr_build_blocks(RowPtrView rp, int64_t n_rows, int64_t &n_
   }
   b.push_back(n_rows);
   return b;
+}
+
+std::vector<int64_t> csr_block_table(RowPtrView rp, int64_t n_rows, int64_t &n_blocks, int64_t &n_long) {
+  const std::vector<int64_t> b = csr_build_blocks(rp, n_rows, n_long);
+  n_blocks = static_cast<int64_t>(b.size()) - 1;
+  std::vector<int64_t> bp(2 * b.size());
+  for (size_t k = 0; k < b.size(); ++k) {
+    bp[2 * k] = b[k];
+    bp[2 * k + 1] = rp[b[k]];
+  }
+  return bp;
 }
 
 // SELL layout (see k_spmv_sell): LHPC_ERR_UNSUPPORTED when a row has more
@@ -584,59 +595,44 @@ static int sell_finish(lhpc_spmv_plan *p, const std::vector<int64_t> &off, int w
   return LHPC_OK;
 }
 
-int sell_build(lhpc_spmv_plan *p, RowPtrView rp, const int32_t *col_idx, const void *val, size_t tsz, bool forced) {
+int sell_build(lhpc_spmv_plan *p, const CsrSource &src, size_t tsz, bool forced) {
   const int64_t n = p->n_rows;
   std::vector<int64_t> off;
   int wmax = 0;
-  LHPC_TRY(sell_offsets(rp, n, p->nnz, tsz, forced, off, wmax));
-  const int64_t total = off.back();
-  std::vector<int32_t> c(static_cast<size_t>(total), -1);
-  std::vector<unsigned char> v(static_cast<size_t>(total) * tsz, 0);
-  const unsigned char *vin = static_cast<const unsigned char *>(val);
-  for (int64_t i = 0; i < n; ++i) {
-    const int64_t b = off[static_cast<size_t>(i / kWave)] + (i % kWave), k0 = rp[i], len = rp[i + 1] - k0;
-    for (int64_t j = 0; j < len; ++j) {
-      c[static_cast<size_t>(b + j * kWave)] = col_idx[k0 + j];
-      std::memcpy(&v[static_cast<size_t>(b + j * kWave) * tsz], vin + static_cast<size_t>(k0 + j) * tsz, tsz);
-    }
-  }
-  LHPC_TRY(dmalloc(reinterpret_cast<void **>(&p->d_col), static_cast<size_t>(total) * 4, p->bytes));
-  LHPC_TRY(dmalloc(&p->d_val, static_cast<size_t>(total) * tsz, p->bytes));
-  LHPC_TRY(dmalloc(reinterpret_cast<void **>(&p->d_blocks), off.size() * 8, p->bytes));
-  if (total) {
-    LHPC_HIP_TRY(hipMemcpy(p->d_col, c.data(), c.size() * 4, hipMemcpyHostToDevice));
-    LHPC_HIP_TRY(hipMemcpy(p->d_val, v.data(), v.size(), hipMemcpyHostToDevice));
-  }
-  return sell_finish(p, off, wmax);
-}
-
-int sell_build_device(lhpc_spmv_plan *p, RowPtrView rp_host, const void *d_rp, const int32_t *d_col,
-                      const void *d_val, size_t tsz, bool forced) {
-  const int64_t n = p->n_rows;
-  std::vector<int64_t> off;
-  int wmax = 0;
-  LHPC_TRY(sell_offsets(rp_host, n, p->nnz, tsz, forced, off, wmax));
+  LHPC_TRY(sell_offsets(src.rp, n, p->nnz, tsz, forced, off, wmax));
   const int64_t total = off.back();
   LHPC_TRY(dmalloc(reinterpret_cast<void **>(&p->d_col), static_cast<size_t>(total) * 4, p->bytes));
   LHPC_TRY(dmalloc(&p->d_val, static_cast<size_t>(total) * tsz, p->bytes));
   LHPC_TRY(dmalloc(reinterpret_cast<void **>(&p->d_blocks), off.size() * 8, p->bytes));
-  LHPC_TRY(sell_finish(p, off, wmax));  // the slice offsets, which the scatter reads
-  if (total) {
+  LHPC_TRY(sell_finish(p, off, wmax));  // the slice offsets, which the device scatter reads
+  if (!total) return LHPC_OK;
+  if (src.d_rp) {  // device CSR: padding first, then one thread per row scatters it
     LHPC_HIP_TRY(hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(p->d_col), -1, static_cast<size_t>(total)));
     LHPC_HIP_TRY(hipMemset(p->d_val, 0, static_cast<size_t>(total) * tsz));
     const unsigned grid = static_cast<unsigned>(std::min<int64_t>((n + kBlock - 1) / kBlock, 65536));
     if (tsz == 4)
-      hipLaunchKernelGGL((k_sell_scatter<uint32_t>), dim3(grid), dim3(kBlock), 0, nullptr, d_rp, rp_host.bits, d_col,
-                         static_cast<const uint32_t *>(d_val), p->d_blocks, n, p->d_col,
+      hipLaunchKernelGGL((k_sell_scatter<uint32_t>), dim3(grid), dim3(kBlock), 0, nullptr, src.d_rp, src.rp.bits,
+                         src.col, static_cast<const uint32_t *>(src.val), p->d_blocks, n, p->d_col,
                          static_cast<uint32_t *>(p->d_val));
     else
-      hipLaunchKernelGGL((k_sell_scatter<uint64_t>), dim3(grid), dim3(kBlock), 0, nullptr, d_rp, rp_host.bits, d_col,
-                         static_cast<const uint64_t *>(d_val), p->d_blocks, n, p->d_col,
+      hipLaunchKernelGGL((k_sell_scatter<uint64_t>), dim3(grid), dim3(kBlock), 0, nullptr, src.d_rp, src.rp.bits,
+                         src.col, static_cast<const uint64_t *>(src.val), p->d_blocks, n, p->d_col,
                          static_cast<uint64_t *>(p->d_val));
     LHPC_HIP_TRY(hipGetLastError());
-    LHPC_HIP_TRY(hipDeviceSynchronize());
+    return static_cast<int>(hipDeviceSynchronize());
   }
-  return LHPC_OK;
+  std::vector<int32_t> c(static_cast<size_t>(total), -1);
+  std::vector<unsigned char> v(static_cast<size_t>(total) * tsz, 0);
+  const unsigned char *vin = static_cast<const unsigned char *>(src.val);
+  for (int64_t i = 0; i < n; ++i) {
+    const int64_t b = off[static_cast<size_t>(i / kWave)] + (i % kWave), k0 = src.rp[i], len = src.rp[i + 1] - k0;
+    for (int64_t j = 0; j < len; ++j) {
+      c[static_cast<size_t>(b + j * kWave)] = src.col[k0 + j];
+      std::memcpy(&v[static_cast<size_t>(b + j * kWave) * tsz], vin + static_cast<size_t>(k0 + j) * tsz, tsz);
+    }
+  }
+  LHPC_HIP_TRY(hipMemcpy(p->d_col, c.data(), c.size() * 4, hipMemcpyHostToDevice));
+  return static_cast<int>(hipMemcpy(p->d_val, v.data(), v.size(), hipMemcpyHostToDevice));
 }
 
 int csr_launch(const lhpc_spmv_plan *p, const void *x, void *y, hipStream_t s) {

@@ -1,6 +1,8 @@
 // lhpc_spmv_impl.hpp — the SpMV plan object and the interface between the
 // kernel-family translation units:
-//   lhpc_spmv.hip         plan creation (kernel selection), the C ABI
+//   lhpc_spmv.hip         plan creation (one flow for host and device input,
+//                         the family chosen by lhpc_plan.hpp spmv_family_policy),
+//                         the C ABI
 //   lhpc_spmv_csr.hip     ROWGROUP / ADAPTIVE (CSR kept as is), SELL (short rows)
 //   lhpc_spmv_xslice.hip  XSLICE (XCD-local column slices + partial reduce)
 //   lhpc_spmv_xtile.hip   XTILE (x tiles in LDS: tile gather + chunk reduce)
@@ -17,6 +19,7 @@
 #include <vector>
 
 #include "lhpc_common.hpp"
+#include "lhpc_plan.hpp"
 
 struct lhpc_spmv_plan {
   lhpc_options opt{};  // resolved variant options (lhpc::resolve_options)
@@ -110,7 +113,6 @@ struct lhpc_spmv_plan {
 namespace lhpc {
 
 constexpr int kBlock = 256;
-constexpr int kSellMaxW = 8;  // SELL: nonzeros per row at most (ADAPTIVE's 2048 / 256)
 
 // Host view of row_ptr regardless of width.
 struct RowPtrView {
@@ -119,6 +121,17 @@ struct RowPtrView {
   int64_t operator[](int64_t i) const {
     return bits == 64 ? static_cast<const int64_t *>(p)[i] : static_cast<const int32_t *>(p)[i];
   }
+};
+
+// The CSR arrays a plan is built from.  rp is always readable on the host;
+// d_rp null: col / val are host arrays; d_rp set (LHPC_PLAN_DEVICE_INPUT, or
+// uploaded copies): col / val and d_rp = row_ptr in rp.bits words live in HBM
+// of the plan's device and rp views a host copy of row_ptr.
+struct CsrSource {
+  RowPtrView rp;
+  const int32_t *col;
+  const void *val;
+  const void *d_rp;
 };
 
 // hipMalloc that books the bytes on the plan; LHPC_ERR_ALLOC on OOM.
@@ -198,13 +211,14 @@ int csr_launch_dot(lhpc_spmv_plan *p, const void *x, void *y, const void *w, dou
 int sell_cg_step(lhpc_spmv_plan *p, const void *r, const void *p_old, void *p_new, void *x, void *q,
                  const double *anum, const double *aden, const double *bnum, const double *bden, double *pq,
                  hipStream_t s);
-// SELL layout; LHPC_ERR_UNSUPPORTED when the rows do not suit it (caller falls back)
-int sell_build(lhpc_spmv_plan *p, RowPtrView rp, const int32_t *col_idx, const void *val, size_t tsz, bool forced);
-// the same layout from device CSR (d_rp: row_ptr of rp_host.bits on the device; rp_host: its host copy)
-int sell_build_device(lhpc_spmv_plan *p, RowPtrView rp_host, const void *d_rp, const int32_t *d_col,
-                      const void *d_val, size_t tsz, bool forced);
-// ADAPTIVE row blocks (≤ 2048 nonzeros and ≤ 256 rows, or one long row)
-std::vector<int64_t> csr_build_blocks(RowPtrView rp, int64_t n_rows, int64_t &n_long);
+// SELL layout, scattered on the host or (device source) on the GPU into the
+// same bytes; LHPC_ERR_UNSUPPORTED when the rows do not suit it (caller falls back)
+int sell_build(lhpc_spmv_plan *p, const CsrSource &src, size_t tsz, bool forced);
+// ADAPTIVE row blocks (csr_build_blocks: ≤ 2048 nonzeros and ≤ 256 rows, or one
+// long row) as the device table: {first row, its row_ptr} per block boundary, so a
+// block reads its row and nonzero range with one 32-B load (no dependent
+// row_ptr round trip); n_blocks = pairs − 1
+std::vector<int64_t> csr_block_table(RowPtrView rp, int64_t n_rows, int64_t &n_blocks, int64_t &n_long);
 
 // ---- lhpc_spmv_xslice.hip
 int xslice_launch(const lhpc_spmv_plan *p, const void *x, void *y, hipStream_t s);
@@ -225,10 +239,9 @@ int xtile_column_parts(lhpc_spmv_plan *p, const int64_t *col_end, int n_parts);
 // with lhpc_dist_chain_parts)
 int xtile_part_of_tile(int64_t tile, int64_t tile_width, int64_t n_cols, const int64_t *col_end, int n_parts);
 int xtile_stage_part(const lhpc_spmv_plan *p, const void *x, int j, hipStream_t s);
-// LHPC_ERR_UNSUPPORTED: the layout does not fit its index types (caller falls back)
-int xtile_build(lhpc_spmv_plan *p, RowPtrView rp, const int32_t *col_idx, const void *val, size_t tsz);
-// the same layout from device-resident col/val (rp: a host copy of row_ptr);
-// LHPC_ERR_UNSUPPORTED for options the device build lacks (aligned segments)
-int xtile_build_device(lhpc_spmv_plan *p, RowPtrView rp_host, const int32_t *d_col, const void *d_val, size_t tsz);
+// LHPC_ERR_UNSUPPORTED: the layout does not fit its index types (caller falls
+// back); a device source builds the same layout on the GPU and also refuses
+// the options that build lacks (aligned segments)
+int xtile_build(lhpc_spmv_plan *p, const CsrSource &src);
 
 }  // namespace lhpc

@@ -1347,12 +1347,8 @@ int xtile_stage_part(const lhpc_spmv_plan *p, const void *x, int j, hipStream_t 
   return XT_TYPED(p, launch_gather, p, x, s, p->xt_cpf[j], p->xt_cpf[j + 1], p->d_pieces_cp);
 }
 
-int xtile_build(lhpc_spmv_plan *p, RowPtrView rp, const int32_t *col_idx, const void *val, size_t tsz) {
-  return tsz == 4 ? build_t<float>(p, rp, col_idx, val, false) : build_t<double>(p, rp, col_idx, val, false);
-}
-
-int xtile_build_device(lhpc_spmv_plan *p, RowPtrView rp_host, const int32_t *d_col, const void *d_val, size_t tsz) {
-  return tsz == 4 ? build_t<float>(p, rp_host, d_col, d_val, true) : build_t<double>(p, rp_host, d_col, d_val, true);
+int xtile_build(lhpc_spmv_plan *p, const CsrSource &src) {
+  return XT_TYPED(p, build_t, p, src.rp, src.col, src.val, src.d_rp != nullptr);
 }
 
 }  // namespace lhpc

@@ -408,6 +408,107 @@ void check_xtile_policy() {
   }
 }
 
+// The kernel-family decision of plan creation (lhpc_plan.hpp
+// spmv_wants_locality, spmv_family_policy).  Expected values are read off the
+// plan creation code as it was before these functions existed (one copy for
+// host arrays, one for device arrays), HAND-DERIVED.  Defaults: fp32, no
+// flags, automatic options, no user splits, 100000 rows, 500000 nonzeros,
+// longest row 5; stages are listed in the order they are attempted.
+void check_spmv_family_policy() {
+  constexpr unsigned RG = LHPC_PLAN_FORCE_ROWGROUP, AD = LHPC_PLAN_FORCE_ADAPTIVE, XS = LHPC_PLAN_FORCE_XSLICE,
+                     XT = LHPC_PLAN_FORCE_XTILE, SE = LHPC_PLAN_FORCE_SELL;
+  constexpr int ADAPTIVE = LHPC_KERNEL_ADAPTIVE, ROWGROUP = LHPC_KERNEL_ROWGROUP;
+  struct Case {
+    const char *name;
+    unsigned flags;
+    size_t elem_bytes;
+    int64_t n_rows, n_cols, nnz, max_row_len;
+    double lines_per_nnz;
+    void (*set)(lhpc_options &);
+    // expected
+    bool wants, xtile, xslice, sell, force_sell;
+    int kernel, L, R, csr_status;  // L = 0: not compared (ADAPTIVE has no shape)
+  };
+  const int64_t N = 100000, Z = 500000;
+  const Case cases[] = {
+      // the 8.0e6-byte threshold of x is strict
+      {"x = 8.0e6 B", 0, 4, N, 2000000, Z, 5, 1.0, nullptr, false, false, false, true, false, ADAPTIVE, 0, 0, 0},
+      {"x = 8.0e6 B + 4", 0, 4, N, 2000001, Z, 5, 0.0, nullptr, true, false, false, true, false, ADAPTIVE, 0, 0, 0},
+      {"fp64 x = 8.0e6 B", 0, 8, N, 1000000, Z, 5, 1.0, nullptr, false, false, false, true, false, ADAPTIVE, 0, 0, 0},
+      {"fp64 x = 8.0e6 B + 8", 0, 8, N, 1000001, Z, 5, 0.0, nullptr, true, false, false, true, false, ADAPTIVE, 0, 0, 0},
+      // local at the threshold (> is strict), not local above it
+      {"lines 0.25", 0, 4, N, 3000000, Z, 5, 0.25, nullptr, true, false, false, true, false, ADAPTIVE, 0, 0, 0},
+      {"lines 0.26", 0, 4, N, 3000000, Z, 5, 0.26, nullptr, true, true, true, true, false, ADAPTIVE, 0, 0, 0},
+      {"locality 0.5, lines 0.4", 0, 4, N, 3000000, Z, 5, 0.4, [](lhpc_options &o) { o.spmv_locality = 0.5; },
+       true, false, false, true, false, ADAPTIVE, 0, 0, 0},
+      {"locality 0.5, lines 0.6", 0, 4, N, 3000000, Z, 5, 0.6, [](lhpc_options &o) { o.spmv_locality = 0.5; },
+       true, true, true, true, false, ADAPTIVE, 0, 0, 0},
+      {"no xtile", 0, 4, N, 3000000, Z, 5, 1.0, [](lhpc_options &o) { o.spmv_no_xtile = 1; },
+       true, false, true, true, false, ADAPTIVE, 0, 0, 0},
+      {"not local, nnz 0", 0, 4, N, 3000000, 0, 0, 1.0, nullptr, true, true, false, true, false, ADAPTIVE, 0, 0, 0},
+      {"no rows", 0, 4, 0, 3000000, 0, 0, 1.0, nullptr, true, false, false, false, false, ADAPTIVE, 0, 0, 0},
+      // forced families: no automatic choice beside them
+      {"force xtile, small x", XT, 4, N, N, Z, 5, 1.0, nullptr, false, true, false, false, false, ADAPTIVE, 0, 0, 0},
+      {"force xslice", XS, 4, N, N, Z, 5, 1.0, nullptr, false, false, true, false, false, ADAPTIVE, 0, 0, 0},
+      {"force sell, longest 8", SE, 4, N, N, Z, 8, 1.0, nullptr, false, false, false, true, true, ADAPTIVE, 0, 0, 0},
+      {"force sell, longest 9", SE, 4, N, N, Z, 9, 1.0, nullptr, false, false, false, false, true, ADAPTIVE, 0, 0, 0},
+      {"force sell, no rows", SE, 4, 0, N, 0, 0, 1.0, nullptr, false, false, false, false, true, ADAPTIVE, 0, 0, 0},
+      {"auto, longest 9", 0, 4, N, N, Z, 9, 1.0, nullptr, false, false, false, false, false, ADAPTIVE, 0, 0, 0},
+      {"no sell", 0, 4, N, N, Z, 5, 1.0, [](lhpc_options &o) { o.spmv_no_sell = 1; },
+       false, false, false, false, false, ADAPTIVE, 0, 0, 0},
+      {"force rowgroup", RG, 4, N, N, Z, 5, 1.0, nullptr, false, false, false, false, false, ROWGROUP, 8, 4, 0},
+      {"force rowgroup + adaptive", RG | AD, 4, N, N, Z, 5, 1.0, nullptr, false, false, false, false, false, ADAPTIVE, 0, 0, 0},
+      // ROWGROUP's shape from the mean row length
+      {"rowgroup mean 4", RG, 4, N, N, 4 * N, 5, 1.0, nullptr, false, false, false, false, false, ROWGROUP, 4, 1, 0},
+      {"rowgroup mean 4.5", RG, 4, N, N, 9 * N / 2, 5, 1.0, nullptr, false, false, false, false, false, ROWGROUP, 8, 4, 0},
+      {"rowgroup mean 16", RG, 4, N, N, 16 * N, 20, 1.0, nullptr, false, false, false, false, false, ROWGROUP, 16, 4, 0},
+      {"rowgroup mean 16.5", RG, 4, N, N, 33 * N / 2, 20, 1.0, nullptr, false, false, false, false, false, ROWGROUP, 32, 2, 0},
+      {"rowgroup mean 32.5", RG, 4, N, N, 65 * N / 2, 40, 1.0, nullptr, false, false, false, false, false, ROWGROUP, 64, 1, 0},
+      // ... or from the options, when lhpc_spmv_csr.hip instantiates the pair
+      {"rowgroup 16 x 8", RG, 4, N, N, Z, 5, 1.0, [](lhpc_options &o) { o.rowgroup_lanes = 16, o.rowgroup_rows = 8; },
+       false, false, false, false, false, ROWGROUP, 16, 8, 0},
+      {"rowgroup 8 x 8", RG, 4, N, N, Z, 5, 1.0, [](lhpc_options &o) { o.rowgroup_lanes = 8, o.rowgroup_rows = 8; },
+       false, false, false, false, false, ROWGROUP, 0, 0, LHPC_ERR_INVALID_ARG},
+      {"rowgroup 8 x 0", RG, 4, N, N, Z, 5, 1.0, [](lhpc_options &o) { o.rowgroup_lanes = 8; },
+       false, false, false, false, false, ROWGROUP, 0, 0, LHPC_ERR_INVALID_ARG},
+      // the shape error waits for the CSR stage: XTILE is tried first
+      {"force xtile + rowgroup 8 x 8", XT | RG, 4, N, N, Z, 5, 1.0,
+       [](lhpc_options &o) { o.rowgroup_lanes = 8, o.rowgroup_rows = 8; },
+       false, true, false, false, false, ROWGROUP, 0, 0, LHPC_ERR_INVALID_ARG},
+  };
+  for (const Case &c : cases) {
+    lhpc_options o{};  // as lhpc_options_init: every choice automatic
+    o.struct_size = sizeof(o);
+    if (c.set) c.set(o);
+    lhpc::SpmvShape s;
+    s.n_rows = c.n_rows;
+    s.n_cols = c.n_cols;
+    s.nnz = c.nnz;
+    s.elem_bytes = c.elem_bytes;
+    s.max_row_len = c.max_row_len;
+    s.lines_per_nnz = c.lines_per_nnz;
+    const bool wants = lhpc::spmv_wants_locality(c.n_cols, c.elem_bytes, c.flags);
+    const lhpc::SpmvFamilyPolicy p = lhpc::spmv_family_policy(s, c.flags, o);
+    const bool ok = wants == c.wants && p.try_xtile == c.xtile && p.try_xslice == c.xslice && p.try_sell == c.sell &&
+                    p.force_sell == c.force_sell && p.csr_kernel == c.kernel && p.csr_status == c.csr_status &&
+                    (c.L == 0 || (p.L == c.L && p.R == c.R));
+    if (!ok)
+      std::fprintf(stderr, "spmv_family_policy %s: wants %d xtile %d xslice %d sell %d force_sell %d kernel %d L %d R %d status %d\n",
+                   c.name, wants, p.try_xtile, p.try_xslice, p.try_sell, p.force_sell, p.csr_kernel, p.L, p.R,
+                   p.csr_status);
+    CHECK(ok);
+  }
+  // the XTILE stage builds what xtile_partition_policy says (user splits: one plan)
+  lhpc_options o{};
+  o.struct_size = sizeof(o);
+  o.xtile_part_nnz = 200000;
+  lhpc::SpmvShape s;
+  s.n_rows = N, s.n_cols = 3000000, s.nnz = Z, s.max_row_len = 5;
+  CHECK(lhpc::spmv_family_policy(s, 0, o).part.parts && lhpc::spmv_family_policy(s, 0, o).part.cap == 200000);
+  s.n_splits = 2;
+  CHECK(!lhpc::spmv_family_policy(s, 0, o).part.parts);
+}
+
 void check_bad_csr() {
   // every builder pass indexes host arrays by col / row_ptr, so validation
   // must reject these before any of them runs (lhpc_spmv_plan_create)
@@ -467,6 +568,7 @@ void check_io(const Csr &a) {
 int main() {
   check_bad_csr();
   check_xtile_policy();
+  check_spmv_family_policy();
   const Csr u = uniform(20000, 30000, 15, 0x5EED0001);
   const Csr p = powerlaw(20000, 20000, 3000, 0x5EED0004);
   const Csr e = uniform(777, 100, 0, 7);  // all rows empty

@@ -885,11 +885,63 @@ def test_device_input_layout_matches_host(lhpc, gpu, case):
     assert dh == dd, [i for i, (a, b) in enumerate(zip(dh, dd)) if a != b]
 
 
+_FAMILY_CASES = {}
+
+
+def _family_case(lhpc, matrix, dtype):
+    """(rp, col, val, x, y oracle) of test_device_and_host_input_give_the_same_plan, built once."""
+    key = (matrix, np.dtype(dtype).name)
+    if key not in _FAMILY_CASES:
+        dt = lhpc.F32 if dtype == np.float32 else lhpc.F64
+        if matrix == "A":  # power-law rows up to 300 nonzeros
+            n_cols = 4133
+            rp, col, val = lhpc.gen_powerlaw_csr(4099, n_cols, lmax=300, dtype=dt, dist=1, seed=0xDE30)
+        else:
+            # 0..5 nonzeros per row, empty rows among them; most rows have 5, so that the
+            # padded slices stream fewer bytes than CSR with its row_ptr and auto takes
+            # SELL (lhpc_spmv_csr.hip sell_offsets: ≈ 0.16 padding entries per row here,
+            # the rule allows ≈ 0.48 in fp32 and ≈ 0.32 in fp64)
+            n_cols = 4099
+            lengths = np.random.default_rng(0xDE31).choice(6, size=4099, p=[0.01, 0.01, 0.01, 0.01, 0.02, 0.94])
+            rp, col, val = _csr_from_lengths(lengths, n_cols, 0xDE32, dyadic=True)
+            val = val.astype(dtype)
+        x = (np.random.default_rng(0xDE33).integers(-8, 9, size=n_cols) / 8.0).astype(dtype)
+        _FAMILY_CASES[key] = (rp, col, val, x, n_cols, S.spmv_oracle(rp, col, val, x)[1])
+    return _FAMILY_CASES[key]
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64], ids=["f32", "f64"])
+@pytest.mark.parametrize("matrix,family", [("A", f) for f in ("auto", "rowgroup", "adaptive", "xslice", "xtile")] +
+                         [("B", "auto"), ("B", "sell")])
+def test_device_and_host_input_give_the_same_plan(lhpc, gpu, matrix, family, dtype):
+    """Every kernel family from device arrays (LHPC_PLAN_DEVICE_INPUT) is the
+    plan host arrays give: equal info(), bit-equal y, and y equal to the
+    oracle's (dyadic values).  XTILE and SELL are built on the GPU from the
+    device arrays; XSLICE, ROWGROUP and ADAPTIVE have no GPU builder, so the
+    library copies A to the host once and goes on with the decision it has
+    already made.  Matrix A: 4099 x 4133 (neither a multiple of 64 or 256),
+    power-law rows up to 300 nonzeros (longer than SELL takes, rows crossing
+    ADAPTIVE's 2048-nonzero blocks); matrix B: 4099 x 4099 with 0..5 nonzeros
+    per row (empty rows), which selects SELL by itself and by flag."""
+    import torch
+    rp, col, val, x, n_cols, want = _family_case(lhpc, matrix, dtype)
+    flags = lhpc.PLAN_FORCE_SELL if family == "sell" else FAMILIES[family]
+    assert (rp[1:] - rp[:-1]).max() > 8 if matrix == "A" else (rp[1:] - rp[:-1]).min() == 0
+    yh, ih = _run(lhpc, gpu, rp, col, val, x, n_cols, flags)
+    dev = [torch.from_numpy(np.ascontiguousarray(a)).to(gpu) for a in (rp, col, val)]
+    yd, idev = _run(lhpc, gpu, *dev, x, n_cols, flags)
+    assert ih == idev
+    assert np.array_equal(yh, yd)
+    assert np.array_equal(yh, want)
+    if family == "auto":
+        assert ih["kernel"] == (lhpc.KERNEL_ADAPTIVE if matrix == "A" else lhpc.KERNEL_SELL)
+
+
 def test_device_input_checks_and_fallbacks(lhpc, gpu):
-    """Device input that does not select XTILE (x fits L2: SELL here) goes
-    through the host path and is exact; malformed device CSR is refused on
-    the GPU with LHPC_ERR_BAD_CSR (a column out of range, a decreasing
-    row_ptr)."""
+    """Device input that does not select XTILE (x fits L2: SELL here, built
+    on the GPU from the device arrays like XTILE) is exact; malformed device
+    CSR is refused on the GPU with LHPC_ERR_BAD_CSR (a column out of range, a
+    decreasing row_ptr)."""
     import torch
     n = 50_000
     rp, col, val = lhpc.gen_uniform_csr(n, n, 5, dtype=lhpc.F32, dist=1, seed=0xDE10)
