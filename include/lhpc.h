@@ -295,6 +295,45 @@ int lhpc_spmv_plan_info_get(const lhpc_spmv_plan *plan,
  * build of the same matrix and options.                                     */
 int lhpc_spmv_plan_layout_digest(const lhpc_spmv_plan *plan, uint64_t *out, int cap, int *n_out);
 /*
+ * Same structure, new values: `val` holds nnz values of the plan's dtype in
+ * the CSR order of the arrays the plan was created from.  Afterwards the plan
+ * computes y = A'·x with A' = (old row_ptr, old col_idx, new val) and is
+ * indistinguishable from a fresh plan built from those arrays with the same
+ * flags and options: the same layout digests (padding included: padding stays
+ * what the build made it, val 0), the same plan info except device_bytes, the
+ * same bits from every call that takes the plan.  Only the values are
+ * rewritten (XTILE: the wave-transposed val runs; SELL: the slices; ADAPTIVE
+ * and ROWGROUP: one copy), none of the index work of a plan build is redone.
+ *   values_on_device != 0   val is an HBM pointer on the plan's device and the
+ *       call is kernel launches or asynchronous copies on `stream` only: no
+ *       allocation, synchronisation or host copy, so it can be captured into a
+ *       graph.  Work issued later on that stream sees the new values; the
+ *       caller orders the call against work on other streams.  One exception:
+ *       a SELL plan keeps no row_ptr, so its first update derives the
+ *       n_rows + 1 row offsets from the layout on the device and keeps them
+ *       with the plan (int64, counted in device_bytes from then on) — that
+ *       one call allocates and synchronises the stream; every later call is
+ *       one kernel launch.
+ *   otherwise               val is a host pointer: the values pass through
+ *       library scratch in HBM where they are re-ordered (XTILE, SELL) or are
+ *       copied straight into place, and the stream is synchronised before
+ *       return.
+ * d_val keeps its address, so a CG graph captured for the plan stays valid
+ * and the next lhpc_cg_solve uses the new values.
+ * Checked before anything is written (a refused call leaves the plan as it
+ * was):
+ *   LHPC_ERR_INVALID_ARG   null plan, null val with nnz > 0, nnz ≠ the plan's
+ *   LHPC_ERR_BUSY          a lhpc_cg_solve is holding the plan
+ *   LHPC_ERR_UNSUPPORTED   XSLICE plans and XTILE column-block plans (a
+ *       value's position in their layout depends on col_idx, which the plan
+ *       does not keep) and single-process multi-device plans (the layout
+ *       spans devices): rebuild the plan instead.  XTILE row parts are
+ *       supported (part i takes the values after the earlier parts').
+ * nnz = 0 or a plan without rows: LHPC_OK, nothing is launched.
+ */
+int lhpc_spmv_plan_set_values(lhpc_spmv_plan *plan, const void *val, int64_t nnz,
+                              int values_on_device, void *stream);
+/*
  * Multi-device plans: y = A·x with full replicas on every device.  x[d]
  * (n_cols) and y[d] (n_rows, not x[d]) are HBM pointers on device d; after
  * the call every y[d] holds the whole y (so y is the next x of an iterative
@@ -444,6 +483,15 @@ int lhpc_spmm(lhpc_spmm_plan *plan, int k, const void *X, int64_t ldx, void *Y, 
  */
 int lhpc_spmm_dot(lhpc_spmm_plan *plan, int k, const void *X, int64_t ldx, void *Y, int64_t ldy,
                   const void *W, int64_t ldw, double *dots, void *stream);
+/*
+ * lhpc_spmv_plan_set_values for the SpMM plan, whose val is the caller's in
+ * CSR order: one asynchronous copy on `stream` (device values: nothing else,
+ * capturable; host values: the stream is synchronised before return).
+ * LHPC_ERR_INVALID_ARG as there; LHPC_ERR_BUSY while a lhpc_cg_solve_multi
+ * holds the plan.
+ */
+int lhpc_spmm_plan_set_values(lhpc_spmm_plan *plan, const void *val, int64_t nnz,
+                              int values_on_device, void *stream);
 int lhpc_spmm_plan_info_get(const lhpc_spmm_plan *plan, lhpc_spmm_plan_info *info);
 int lhpc_spmm_plan_destroy(lhpc_spmm_plan *plan);
 

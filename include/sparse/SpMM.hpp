@@ -71,6 +71,16 @@ class SpMMPlan {
     lhpc::checkLhpc(lhpc_spmm_plan_info_get(plan_, &i));
     return i;
   }
+  // Same structure, new values (lhpc_spmm_plan_set_values), as
+  // SpMVPlan<T>::set_values: one copy into the plan's CSR val.
+  void set_values(const T *val, std::int64_t nnz, bool on_device = false, void *stream = nullptr) {
+    lhpc::checkLhpc(lhpc_spmm_plan_set_values(plan_, val, nnz, on_device ? 1 : 0, stream));
+  }
+  template <typename OffsetT>
+  void set_values(const CSRMatrix<T, std::int32_t, OffsetT> &A) {
+    if (A.n_rows != n_rows_ || A.n_cols != n_cols_) lhpc::throwLhpcError(LHPC_ERR_INVALID_ARG, __FILE__, __LINE__);
+    set_values(A.val.data(), static_cast<std::int64_t>(A.nnz()));
+  }
   std::int64_t rows() const noexcept { return n_rows_; }
   std::int64_t cols() const noexcept { return n_cols_; }
   lhpc_spmm_plan *native() noexcept { return plan_; }

@@ -103,6 +103,20 @@ class SpMVPlan {
     lhpc::checkLhpc(lhpc_spmv_plan_info_get(plan_, &i));
     return i;
   }
+  // Same structure, new values (lhpc_spmv_plan_set_values): nnz values in the
+  // CSR order the plan was built from, a host pointer (synchronous) or, with
+  // on_device, an HBM pointer on the plan's device (asynchronous on `stream`).
+  // The plan then equals a fresh plan built from the new values.  XSLICE,
+  // column-block and multi-device plans throw (LHPC_ERR_UNSUPPORTED).
+  void set_values(const T *val, std::int64_t nnz, bool on_device = false, void *stream = nullptr) {
+    lhpc::checkLhpc(lhpc_spmv_plan_set_values(plan_, val, nnz, on_device ? 1 : 0, stream));
+  }
+  // … from a host matrix of the plan's shape and structure (only A.val is read)
+  template <typename OffsetT>
+  void set_values(const CSRMatrix<T, std::int32_t, OffsetT> &A) {
+    if (A.n_rows != n_rows_ || A.n_cols != n_cols_) lhpc::throwLhpcError(LHPC_ERR_INVALID_ARG, __FILE__, __LINE__);
+    set_values(A.val.data(), static_cast<std::int64_t>(A.nnz()));
+  }
   std::int64_t rows() const noexcept { return n_rows_; }
   std::int64_t cols() const noexcept { return n_cols_; }
   int devices() const noexcept { return n_devices_; }

@@ -74,6 +74,7 @@ ABI_SYMBOLS = (
     "lhpc_spmv_plan_layout_digest", "lhpc_dist_rccl_calls",
     "lhpc_spmm_plan_create", "lhpc_spmm", "lhpc_spmm_plan_info_get", "lhpc_spmm_plan_destroy",
     "lhpc_spmm_dot", "lhpc_cg_solve_multi",
+    "lhpc_spmv_plan_set_values", "lhpc_spmm_plan_set_values",
 )
 
 if not os.path.exists(LIB_PATH):
@@ -209,6 +210,8 @@ _sig("lhpc_spmv_multi", _i, _p, _p, _p, _p)
 _sig("lhpc_spmv_plan_layout_digest", _i, _p, _p, _i, C.POINTER(_i))
 _sig("lhpc_spmv_plan_multi_info", _i, _p, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), _p, _p)
 _sig("lhpc_spmv_plan_destroy", _i, _p)
+_sig("lhpc_spmv_plan_set_values", _i, _p, _p, _i64, _i, _p)
+_sig("lhpc_spmm_plan_set_values", _i, _p, _p, _i64, _i, _p)
 _sig("lhpc_spmm_plan_create", _i, C.POINTER(_p), _i, _i64, _i64, _i64, _p, _i, _p, _p, _i, _u)
 _sig("lhpc_spmm", _i, _p, _i, _p, _i64, _p, _i64, _i, _p)
 _sig("lhpc_spmm_dot", _i, _p, _i, _p, _i64, _p, _i64, _p, _i64, _p, _p)
@@ -327,6 +330,36 @@ def _stream_ptr(stream) -> Optional[int]:
 
 
 # ------------------------------------------------------------ SpMV
+def _set_values(plan, fn, name, val, stream):
+    """``plan.set_values(val, stream)`` of both plan classes: ``val`` is a host
+    numpy array or a CUDA tensor on the plan's device, nnz values of the
+    plan's dtype; anything else is rejected here, before the C call."""
+    if _is_torch(val):
+        import torch
+        if val.dtype != (torch.float32 if plan.dtype == F32 else torch.float64):
+            raise TypeError(f"set_values: expected dtype {plan.np_dtype}, got {val.dtype}")
+        if not val.is_cuda:
+            raise ValueError("set_values: a torch tensor must be on the plan's device (pass host values as numpy)")
+        if val.dim() != 1 or int(val.numel()) != plan.nnz:
+            raise ValueError(f"set_values: expected {plan.nnz} values, got shape {tuple(val.shape)}")
+        dev = plan.info()["device"]
+        if getattr(plan, "devices", None) is None and val.device.index != dev:
+            raise ValueError(f"set_values: values on cuda:{val.device.index}, plan on device {dev}")
+    elif isinstance(val, np.ndarray):
+        if val.dtype != plan.np_dtype:
+            raise TypeError(f"set_values: expected dtype {plan.np_dtype}, got {val.dtype}")
+        if val.ndim != 1 or int(val.size) != plan.nnz:
+            raise ValueError(f"set_values: expected {plan.nnz} values, got shape {val.shape}")
+    else:
+        raise TypeError(f"set_values: expected numpy array or torch tensor, got {type(val)}")
+    ptr, on_dev = _buf(val)
+    if on_dev and stream is None:
+        import torch
+        stream = torch.cuda.current_stream(val.device)
+    _check(fn(plan._h, ptr if plan.nnz else None, plan.nnz, int(on_dev), _stream_ptr(stream)), name)
+    return plan
+
+
 def _csr_arrays(row_ptr, col_idx, val):
     """The CSR arrays of a plan constructor: host numpy arrays (row_ptr
     int32/int64, col_idx int32, val float32/float64), or contiguous CUDA
@@ -498,6 +531,18 @@ class SpMVPlan:
         _check(lib.lhpc_spmv_range(self._h, int(k), y_k.data_ptr(), _stream_ptr(stream)), "lhpc_spmv_range")
         return y_k
 
+    def set_values(self, val, stream=None):
+        """Same structure, new values (lhpc_spmv_plan_set_values): ``val`` holds
+        nnz values of the plan's dtype in the CSR order the plan was built
+        from.  A numpy array is staged through HBM and the call returns
+        synchronised; a CUDA tensor on the plan's device is taken in place,
+        asynchronously on ``stream`` (default: torch's current stream) and
+        without allocation (a SELL plan's first update excepted).  The plan
+        then equals a fresh plan built from the new values.  XSLICE,
+        column-block and multi-device plans raise LhpcError
+        (LHPC_ERR_UNSUPPORTED) and stay as they were: rebuild those."""
+        return _set_values(self, lib.lhpc_spmv_plan_set_values, "lhpc_spmv_plan_set_values", val, stream)
+
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
             lib.lhpc_spmv_plan_destroy(self._h)
@@ -608,6 +653,11 @@ class SpMMPlan:
             stream = torch.cuda.current_stream(Y.device)
         _check(lib.lhpc_spmm(self._h, k, xp, ldx, yp, ldy, int(xd), _stream_ptr(stream)), "lhpc_spmm")
         return Y
+
+    def set_values(self, val, stream=None):
+        """Same structure, new values (lhpc_spmm_plan_set_values): as
+        ``SpMVPlan.set_values``; one copy into the plan's CSR val."""
+        return _set_values(self, lib.lhpc_spmm_plan_set_values, "lhpc_spmm_plan_set_values", val, stream)
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:

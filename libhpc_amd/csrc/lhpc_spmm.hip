@@ -557,6 +557,24 @@ extern "C" int lhpc_spmm_dot(lhpc_spmm_plan *p, int k, const void *X, int64_t ld
   } LHPC_ABI_CATCH
 }
 
+// the plan's val is the caller's in CSR order: one copy, nothing re-encoded
+extern "C" int lhpc_spmm_plan_set_values(lhpc_spmm_plan *p, const void *val, int64_t nnz, int values_on_device,
+                                         void *stream) {
+  try {
+    if (!p || (nnz > 0 && !val) || nnz != p->nnz) return LHPC_ERR_INVALID_ARG;
+    if (p->cg_busy.load()) return LHPC_ERR_BUSY;
+    if (nnz == 0 || p->n_rows == 0) return LHPC_OK;
+    RocTxRange rx("lhpc_spmm_plan_set_values");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    LHPC_HIP_TRY(hipSetDevice(p->device));
+    const size_t bytes = static_cast<size_t>(nnz) * (p->dtype == LHPC_F32 ? 4 : 8);
+    LHPC_HIP_TRY(hipMemcpyAsync(p->d_val, val, bytes,
+                                values_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+    if (!values_on_device) LHPC_HIP_TRY(hipStreamSynchronize(s));
+    return LHPC_OK;
+  } LHPC_ABI_CATCH
+}
+
 extern "C" int lhpc_spmm_plan_info_get(const lhpc_spmm_plan *p, lhpc_spmm_plan_info *info) {
   try {
     if (!p || !info) return LHPC_ERR_INVALID_ARG;

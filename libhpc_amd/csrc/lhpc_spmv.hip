@@ -642,6 +642,76 @@ extern "C" int lhpc_spmv_dot(lhpc_spmv_plan *p, const void *x, void *y, const vo
   } LHPC_ABI_CATCH
 }
 
+namespace lhpc {
+namespace {
+// Which plans can take new values in place: those whose layout positions are
+// a function of row_ptr alone.  XSLICE and XTILE column blocks place a value
+// by its column, which the plan does not keep; a multi-device plan spans
+// devices.  (Every part of a plan of parts has a part_col entry: a row part
+// starts at column 0 and covers every column.)
+int set_values_supported(const lhpc_spmv_plan *p) {
+  if (p->multi) return LHPC_ERR_UNSUPPORTED;
+  if (!p->parts.empty()) {
+    int64_t sum = 0;
+    for (size_t i = 0; i < p->parts.size(); ++i) {
+      const lhpc_spmv_plan *q = p->parts[i];
+      if (p->part_col[i] != 0 || q->n_cols != p->n_cols || q->xt_acc) return LHPC_ERR_UNSUPPORTED;
+      sum += q->nnz;
+    }
+    return sum == p->nnz ? LHPC_OK : LHPC_ERR_UNSUPPORTED;
+  }
+  return p->kernel == LHPC_KERNEL_XSLICE ? LHPC_ERR_UNSUPPORTED : LHPC_OK;
+}
+
+// val in HBM of the plan's device; launches and asynchronous copies on s only
+// (but for a SELL plan's first update, lhpc_spmv_csr.hip sell_set_values)
+int set_values_device(lhpc_spmv_plan *p, const void *val, hipStream_t s) {
+  const size_t tsz = p->dtype == LHPC_F32 ? 4 : 8;
+  if (!p->parts.empty()) {  // row parts: part i takes the values after the earlier parts'
+    int64_t off = 0;
+    for (const lhpc_spmv_plan *q : p->parts) {
+      LHPC_TRY(xtile_set_values(q, static_cast<const unsigned char *>(val) + off * static_cast<int64_t>(tsz), s));
+      off += q->nnz;
+    }
+    return LHPC_OK;
+  }
+  if (p->kernel == LHPC_KERNEL_XTILE) return xtile_set_values(p, val, s);
+  if (p->kernel == LHPC_KERNEL_SELL) return sell_set_values(p, val, s);
+  // ADAPTIVE / ROWGROUP: d_val is val in CSR order
+  LHPC_HIP_TRY(hipMemcpyAsync(p->d_val, val, static_cast<size_t>(p->nnz) * tsz, hipMemcpyDeviceToDevice, s));
+  return LHPC_OK;
+}
+}  // namespace
+}  // namespace lhpc
+
+extern "C" int lhpc_spmv_plan_set_values(lhpc_spmv_plan *p, const void *val, int64_t nnz, int values_on_device,
+                                         void *stream) {
+  try {
+    if (!p || (nnz > 0 && !val) || nnz != p->nnz) return LHPC_ERR_INVALID_ARG;
+    if (p->cg_busy.load()) return LHPC_ERR_BUSY;
+    LHPC_TRY(set_values_supported(p));
+    if (nnz == 0 || p->n_rows == 0) return LHPC_OK;
+    RocTxRange rx("lhpc_spmv_plan_set_values");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    LHPC_HIP_TRY(hipSetDevice(p->device));
+    if (values_on_device) return set_values_device(p, val, s);
+    const size_t bytes = static_cast<size_t>(nnz) * (p->dtype == LHPC_F32 ? 4 : 8);
+    if (p->parts.empty() && p->kernel != LHPC_KERNEL_XTILE && p->kernel != LHPC_KERNEL_SELL) {
+      // CSR order in the plan too: straight into place
+      LHPC_HIP_TRY(hipMemcpyAsync(p->d_val, val, bytes, hipMemcpyHostToDevice, s));
+      LHPC_HIP_TRY(hipStreamSynchronize(s));
+      return LHPC_OK;
+    }
+    void *tmp = nullptr;  // stream-ordered library scratch, freed before return
+    LHPC_HIP_TRY(scratch_alloc(&tmp, bytes, s));
+    hipError_t e = hipMemcpyAsync(tmp, val, bytes, hipMemcpyHostToDevice, s);
+    const int st = e == hipSuccess ? set_values_device(p, tmp, s) : static_cast<int>(e);
+    (void)hipFreeAsync(tmp, s);
+    e = hipStreamSynchronize(s);
+    return st != LHPC_OK ? st : static_cast<int>(e);
+  } LHPC_ABI_CATCH
+}
+
 extern "C" int lhpc_spmv_plan_info_get(const lhpc_spmv_plan *p, lhpc_spmv_plan_info *info) {
   try {
     if (!p || !info) return LHPC_ERR_INVALID_ARG;
@@ -697,7 +767,7 @@ extern "C" int lhpc_spmv_plan_destroy(lhpc_spmv_plan *p) {
                     static_cast<void *>(p->d_seghi), static_cast<void *>(p->d_seg), static_cast<void *>(p->d_pieces), static_cast<void *>(p->d_cont),
                     static_cast<void *>(p->d_col16), static_cast<void *>(p->d_perm), p->d_xg,
                     static_cast<void *>(p->d_pieces_cp), static_cast<void *>(p->d_pext),
-                    static_cast<void *>(p->d_carry)})
+                    static_cast<void *>(p->d_carry), static_cast<void *>(p->d_sell_rp)})
       if (q) (void)hipFree(q);
     if (p->h_scalars) (void)hipHostFree(p->h_scalars);
     for (hipGraphExec_t g : p->cg_graph)

@@ -33,6 +33,9 @@ struct lhpc_spmv_plan {
   int64_t *d_blocks = nullptr;  // ADAPTIVE: the block table; SELL: the slice offsets
   int64_t n_blocks = 0, n_long = 0;
   int sell_w = 0;              // SELL: widest slice
+  // SELL, lhpc_spmv_plan_set_values: the n_rows + 1 CSR row offsets (int64),
+  // derived from the layout on the first update (the plan keeps no row_ptr)
+  int64_t *d_sell_rp = nullptr;
   void *d_xstage = nullptr, *d_ystage = nullptr;
   double *h_scalars = nullptr;  // lhpc_cg_solve: 2 pinned host scalars, allocated on first use
   // lhpc_cg_solve's work (first solve; freed with the plan): r, p, q and x
@@ -211,6 +214,9 @@ int csr_launch_dot(lhpc_spmv_plan *p, const void *x, void *y, const void *w, dou
 int sell_cg_step(lhpc_spmv_plan *p, const void *r, const void *p_old, void *p_new, void *x, void *q,
                  const double *anum, const double *aden, const double *bnum, const double *bden, double *pq,
                  hipStream_t s);
+// lhpc_spmv_plan_set_values on a SELL plan: val (HBM, CSR order) into the
+// slices, on s.  The first call derives d_sell_rp (allocates, synchronises s).
+int sell_set_values(lhpc_spmv_plan *p, const void *val, hipStream_t s);
 // SELL layout, scattered on the host or (device source) on the GPU into the
 // same bytes; LHPC_ERR_UNSUPPORTED when the rows do not suit it (caller falls back)
 int sell_build(lhpc_spmv_plan *p, const CsrSource &src, size_t tsz, bool forced);
@@ -231,6 +237,9 @@ int xtile_launch(const lhpc_spmv_plan *p, const void *x, void *y, hipStream_t s)
 int xtile_stage(const lhpc_spmv_plan *p, const void *x, hipStream_t s);
 int xtile_range_gather(const lhpc_spmv_plan *p, const void *x, int k, hipStream_t s);
 int xtile_range(const lhpc_spmv_plan *p, int k, void *yk, hipStream_t s);
+// lhpc_spmv_plan_set_values on one XTILE plan (not a plan of parts): val (HBM,
+// p->nnz values in CSR order) into the wave-transposed runs of d_val, on s
+int xtile_set_values(const lhpc_spmv_plan *p, const void *val, hipStream_t s);
 // column parts: col_end[j] ascending, col_end[n_parts-1] ≥ n_cols; tile t goes
 // to the first part whose bound covers its last column.  LHPC_ERR_UNSUPPORTED
 // for plans that gather per row range (cache-sized ranges).

@@ -1013,6 +1013,63 @@ __global__ __launch_bounds__(64) void k_xt_permute_blocks(const int32_t *__restr
   }
 }
 
+// ------------------------------------------------------------ value refresh
+// lhpc_spmv_plan_set_values: the plan's val runs are val in CSR order,
+// wave-transposed per chunk (xtile_wave_pos), so new values need none of the
+// build's tile ranking.  One wave per wave region (64·RUN chunk positions =
+// 4 KB; kXtSetWaves regions per block): the region's values stream in from
+// val[e0 + i) — contiguous, at any element alignment, 64 consecutive elements
+// per load instruction — into the wave's LDS in the reduce's run layout
+// (xt_slot: run t = lane t's 64 B, 16-B slots swizzled), and each lane reads
+// its run's 16-B vectors back (conflict-free ds_read_b128) and stores vector q
+// at (q·64 + lane)·VW of the region: 1 KB contiguous per store instruction, as
+// the reduce loads them.  Only positions < e1 − e0 are written (the vector
+// holding position m − 1 element by element), so padding stays the build's 0.
+constexpr int kXtSetWaves = 4;
+template <typename T>
+__global__ __launch_bounds__(kXtSetWaves * kWave) void k_xt_set_values(
+    const int32_t *__restrict__ cdesc, const T *__restrict__ val, int64_t nnz, int64_t nrun, T *__restrict__ valt) {
+  constexpr int RUN = xt_run<T>(), VW = 16 / static_cast<int>(sizeof(T)), NV = RUN / VW, REG = kWave * RUN;
+  constexpr int M = XtRed<T, xt_red_blk<T>()>::M, PB = M / REG / kXtSetWaves;  // blocks per chunk
+  static_assert(PB * kXtSetWaves * REG == M, "a chunk's wave regions divide among whole blocks");
+  typedef T lvec __attribute__((ext_vector_type(VW)));
+  __shared__ __align__(16) T xs[kXtSetWaves][REG];
+  const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
+  const int64_t c = blockIdx.x / PB;
+  const int i0 = (static_cast<int>(blockIdx.x % PB) * kXtSetWaves + wv) * REG;  // the region's first chunk position
+  const u32x4 d = *reinterpret_cast<const u32x4 *>(cdesc + 8 * c);
+  const int e0 = static_cast<int>(d[0]), m = static_cast<int>(d[1]) - e0;
+  const int64_t vb = cdesc[8 * c + 4];
+  if (i0 >= m) return;  // wave-uniform (no block barrier below): the chunk has no such region
+  LHPC_DEVICE_CHECK(e0 >= 0 && m <= M && static_cast<int64_t>(e0) + m <= nnz && vb >= 0 && vb + i0 + REG <= nrun);
+  T *xw = xs[wv];
+  T v[RUN];
+#pragma unroll
+  for (int k = 0; k < RUN; ++k) {
+    const int i = i0 + k * kWave + lane;
+    v[k] = i < m ? ld_stream(val + e0 + i) : T(0);
+  }
+#pragma unroll
+  for (int k = 0; k < RUN; ++k) xw[xt_slot<T>(k * kWave + lane)] = v[k];
+  __builtin_amdgcn_wave_barrier();  // LDS is in order within a wave: no block barrier needed
+  const lvec *xr = reinterpret_cast<const lvec *>(xw + lane * RUN);
+  const int swz = xt_swz(lane);
+  T *dst = valt + vb + i0;
+#pragma unroll
+  for (int q = 0; q < NV; ++q) {
+    const lvec u = xr[q ^ swz];
+    const int p0 = i0 + lane * RUN + q * VW;  // chunk position of the vector's first element
+    T *a = dst + (q * kWave + lane) * VW;
+    if (p0 + VW <= m) {
+      *reinterpret_cast<lvec *>(a) = u;
+    } else {
+#pragma unroll
+      for (int r = 0; r < VW; ++r)
+        if (p0 + r < m) a[r] = u[r];
+    }
+  }
+}
+
 // ------------------------------------------------------------- plan build
 // Three stages (build_t): policy — every decision, lhpc_plan.hpp xtile_policy;
 // layout — the host tables (XtileHost, run bases) and the plan's O(nnz)
@@ -1345,6 +1402,18 @@ int xtile_column_parts(lhpc_spmv_plan *p, const int64_t *col_end, int n_parts) {
 int xtile_stage_part(const lhpc_spmv_plan *p, const void *x, int j, hipStream_t s) {
   if (p->xt_cpf.empty() || j < 0 || j + 2 > static_cast<int>(p->xt_cpf.size())) return LHPC_ERR_INVALID_ARG;
   return XT_TYPED(p, launch_gather, p, x, s, p->xt_cpf[j], p->xt_cpf[j + 1], p->d_pieces_cp);
+}
+
+template <typename T>
+int set_values_t(const lhpc_spmv_plan *p, const void *val, hipStream_t s) {
+  constexpr int RUN = xt_run<T>(), M = XtRed<T, xt_red_blk<T>()>::M, PB = M / (kWave * RUN) / kXtSetWaves;
+  if (p->xt_C == 0) return LHPC_OK;
+  hipLaunchKernelGGL((k_xt_set_values<T>), dim3(static_cast<unsigned>(p->xt_C * PB)), dim3(kXtSetWaves * kWave), 0, s,
+                     p->d_cdesc, static_cast<const T *>(val), p->nnz, p->xt_nrun, static_cast<T *>(p->d_val));
+  return check_launch(s);
+}
+int xtile_set_values(const lhpc_spmv_plan *p, const void *val, hipStream_t s) {
+  return XT_TYPED(p, set_values_t, p, val, s);
 }
 
 int xtile_build(lhpc_spmv_plan *p, const CsrSource &src) {
