@@ -230,6 +230,15 @@ typedef struct lhpc_options {
    * per chunk; 2 the plan's per-chunk phase-A tables (batch rank terms and
    * segment bases, copied to LDS by LDS-DMA); 0 (auto): 2 for fp64, 1 fp32 */
   int32_t xtile_pretable;
+  /* XTILE fp32 iperm reduce (≤ 512 tiles, no aligned segments): 2 the plan's
+   * per-chunk record (segment-start bitmap, segment bases, row-start bitmap,
+   * copied to LDS by LDS-DMA) instead of the segment scan and the row_ptr
+   * decode of every call; 1 off; 0 (auto): 2 for plans that take cache-sized
+   * ranges by themselves (xg past the Infinity Cache, no user row splits, no
+   * xtile_ranges), else 1.  Plans with an empty row, column
+   * blocks and xtile_pretable = 2 keep the other reduce whatever is asked;
+   * lhpc_spmv_plan_chunkrec tells which one a plan got.                     */
+  int32_t xtile_chunkrec;
 } lhpc_options;
 void lhpc_options_init(lhpc_options *opts);
 
@@ -294,6 +303,12 @@ int lhpc_spmv_plan_info_get(const lhpc_spmv_plan *plan,
  * A plan built from LHPC_PLAN_DEVICE_INPUT has the same digests as the host
  * build of the same matrix and options.                                     */
 int lhpc_spmv_plan_layout_digest(const lhpc_spmv_plan *plan, uint64_t *out, int cap, int *n_out);
+/* Does the plan's XTILE reduce read per-chunk records (options.xtile_chunkrec)?
+ * *on = 1 / 0 (a plan of row parts / column blocks: 1 if any part does);
+ * *digest (may be NULL) = the FNV-1a digest, size folded in, of the records
+ * in HBM, parts folded in order — the same for the host and the device build
+ * of one matrix; the offset basis when there is none.  Other kernels: *on = 0. */
+int lhpc_spmv_plan_chunkrec(const lhpc_spmv_plan *plan, int *on, uint64_t *digest);
 /*
  * Same structure, new values: `val` holds nnz values of the plan's dtype in
  * the CSR order of the arrays the plan was created from.  Afterwards the plan

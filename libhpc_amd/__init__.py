@@ -75,6 +75,7 @@ ABI_SYMBOLS = (
     "lhpc_spmm_plan_create", "lhpc_spmm", "lhpc_spmm_plan_info_get", "lhpc_spmm_plan_destroy",
     "lhpc_spmm_dot", "lhpc_cg_solve_multi",
     "lhpc_spmv_plan_set_values", "lhpc_spmm_plan_set_values",
+    "lhpc_spmv_plan_chunkrec",
 )
 
 if not os.path.exists(LIB_PATH):
@@ -124,7 +125,7 @@ class Options(C.Structure):
                 ("dist_world1", C.c_int32), ("xtile_part_nnz", C.c_int32), ("multi_chunks", C.c_int32),
                 ("multi_exchange", C.c_int32), ("multi_force", C.c_int32), ("dist_reduce_streams", C.c_int32),
                 ("xtile_col_blocks", C.c_int32), ("xtile_host_build", C.c_int32), ("spmv_no_sell", C.c_int32),
-                ("xtile_ring", C.c_int32), ("xtile_pretable", C.c_int32)]
+                ("xtile_ring", C.c_int32), ("xtile_pretable", C.c_int32), ("xtile_chunkrec", C.c_int32)]
 
     def __init__(self, **kw):
         super().__init__()
@@ -208,6 +209,7 @@ _sig("lhpc_spmv_range", _i, _p, _i, _p, _p)
 _sig("lhpc_spmv_plan_info_get", _i, _p, C.POINTER(PlanInfo))
 _sig("lhpc_spmv_multi", _i, _p, _p, _p, _p)
 _sig("lhpc_spmv_plan_layout_digest", _i, _p, _p, _i, C.POINTER(_i))
+_sig("lhpc_spmv_plan_chunkrec", _i, _p, C.POINTER(_i), C.POINTER(C.c_uint64))
 _sig("lhpc_spmv_plan_multi_info", _i, _p, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), _p, _p)
 _sig("lhpc_spmv_plan_destroy", _i, _p)
 _sig("lhpc_spmv_plan_set_values", _i, _p, _p, _i64, _i, _p)
@@ -453,7 +455,19 @@ class SpMVPlan:
     def info(self) -> dict:
         inf = PlanInfo()
         _check(lib.lhpc_spmv_plan_info_get(self._h, C.byref(inf)), "lhpc_spmv_plan_info_get")
-        return inf.as_dict()
+        d = inf.as_dict()
+        on = _i()
+        _check(lib.lhpc_spmv_plan_chunkrec(self._h, C.byref(on), None), "lhpc_spmv_plan_chunkrec")
+        if on.value:  # reported only when on: lhpc_spmv_plan_info has no room for it
+            d["xtile_chunkrec"] = 1
+        return d
+
+    def chunkrec(self):
+        """lhpc_spmv_plan_chunkrec: (1 if the XTILE reduce reads per-chunk
+        records else 0, FNV-1a digest of the records in HBM)."""
+        on, dig = _i(), C.c_uint64()
+        _check(lib.lhpc_spmv_plan_chunkrec(self._h, C.byref(on), C.byref(dig)), "lhpc_spmv_plan_chunkrec")
+        return on.value, int(dig.value)
 
     def layout_digest(self):
         """lhpc_spmv_plan_layout_digest: FNV-1a digests of an XTILE plan's

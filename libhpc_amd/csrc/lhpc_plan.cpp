@@ -354,6 +354,20 @@ XtilePolicy xtile_policy(const XtileShape &s, const lhpc_options &o) {
   // 2.3K of 27.8K cycles per chunk), C2 88.1 → 89.4 µs (the tables' extra
   // 2 KB per chunk outweigh an 8-wave scan)
   r.pre = ip && !al && s.G == 1 && (o.xtile_pretable == 2 || (o.xtile_pretable == 0 && tsz == 8));
+  // chunk records (options.xtile_chunkrec): fp32
+  // iperm plans without aligned segments, G = 1, whose rows all hold a
+  // nonzero and whose reduce stores y (a record has no bit for an empty row,
+  // and the record reduce has no adding store).  Phase-A tables asked for by
+  // option come first: the two exclude each other.  Default: the plans that
+  // take cache-sized ranges by themselves (xg past the Infinity Cache, no
+  // user splits, no xtile_ranges) — same box, two runs each, C2 reduce
+  // 87.6 / 87.8 → 84.4 / 84.5 µs per range and 699.2 / 698.6 → 714.5 / 713.2
+  // GFLOP/s, C4 88.2 / 88.1 → 87.8 / 87.6 µs and 691.6 / 690.1 → 694.6 / 693.9
+  // (profiles/r11).  Per-rank ring plans and plans inside the cache are not
+  // measured: they keep the scan unless asked.
+  const bool rec_auto = r.past_cache && r.ranges > 1 && !user_splits && o.xtile_ranges == 0;
+  r.rec = ip && !al && s.G == 1 && tsz == 4 && !r.pre && !s.empty_rows && !s.y_add &&
+          (o.xtile_chunkrec == 2 || (o.xtile_chunkrec == 0 && rec_auto));
   if (o.xtile_steps > 0) {
     const int u = o.xtile_steps;
     r.steps = u <= 2 ? 2 : u < 8 ? 4 : u < 16 ? 8 : 16;
@@ -728,6 +742,43 @@ void xtile_phase_tables(const XtileHost &o, std::vector<uint32_t> &bt, std::vect
         before += __builtin_popcountll(w);
       }
     }
+  }
+}
+
+bool csr_has_empty_row(const void *rp, int bits, int64_t n_rows) {
+  int any = 0;
+#pragma omp parallel for schedule(static) reduction(| : any)
+  for (int64_t i = 0; i < n_rows; ++i) any |= rp_at(rp, bits, i + 1) == rp_at(rp, bits, i) ? 1 : 0;
+  return any != 0;
+}
+
+void xtile_chunk_records(const XtileHost &o, const void *rp, int bits, std::vector<uint32_t> &rec) {
+  const int64_t S = o.S, C = o.n_chunks, M = o.M, BW = M / 32, RW = xtile_chunkrec_words(o.M, o.S);
+  rec.assign(static_cast<size_t>(std::max<int64_t>(C, 1) * RW), 0u);
+  const int64_t K = static_cast<int64_t>(o.rchunk.size()) - 1;
+#pragma omp parallel for schedule(dynamic, 64)
+  for (int64_t c = 0; c < C; ++c) {
+    int64_t k = 0;  // c's range (for the ring deltas)
+    if (!o.rdelta.empty())
+      while (k + 1 < K && o.rchunk[k + 1] <= c) ++k;
+    uint32_t *bm = rec.data() + c * RW, *sbm = bm + BW;
+    int32_t *bn = reinterpret_cast<int32_t *>(sbm + BW);
+    int64_t flat = 0, nne = 0;
+    for (int64_t s = 0; s < S; ++s) {
+      const int64_t a = o.segoff[c * S + s], len = o.segoff[(c + 1) * S + s] - a;
+      if (len <= 0) continue;
+      const int64_t start = a + (o.rdelta.empty() ? 0 : o.rdelta[static_cast<size_t>(k * S + s)]);
+      bn[nne++] = static_cast<int32_t>(start - flat);
+      sbm[flat >> 5] |= 1u << (flat & 31);
+      flat += len;
+    }
+    for (int64_t r = nne; r < S; ++r) bn[r] = nne > 0 ? bn[nne - 1] : 0;
+    const int64_t e0 = o.ce[c], m = o.ce[c + 1] - e0, r0 = o.cr[c], r1 = o.cr[c + 1];
+    for (int64_t r = r0; r < r1; ++r) {
+      const int64_t i = rp_at(rp, bits, r) - e0;
+      if (i >= 0 && i < m) bm[i >> 5] |= 1u << (i & 31);
+    }
+    bn[S] = rp_at(rp, bits, r1) - e0 > m ? 1 : 0;
   }
 }
 

@@ -197,6 +197,8 @@ struct XtileShape {
   bool dev_build = false;
   int64_t W = 0;
   int G = 1;
+  bool empty_rows = false;  // some row has no nonzeros (csr_has_empty_row)
+  bool y_add = false;       // a column block after the first: the reduce adds into y
 };
 struct XtilePolicy {
   int64_t W = 0, tiles = 0;
@@ -208,6 +210,7 @@ struct XtilePolicy {
   int ranges = 0;                    // cache-sized ranges wanted (≤ 1: none)
   bool own_cuts = false;             // … as `ranges` nnz-balanced row cuts of the plan's own (lhpc_csr_partition_rows)
   bool pre = false;                  // phase-A tables
+  bool rec = false;                  // chunk records (fp32; excludes pre)
   int steps = 8;                     // gather steps in flight
   // by the plan's final range count K (user splits + 1, or the accepted cuts
   // + 1; ≤ 1: no ranges):
@@ -292,6 +295,26 @@ void xtile_ring_pieces(XtileHost &o, int64_t piece_nnz, std::vector<int64_t> &rp
 // positions the rank terms bt[(c·M/64 + b)·4 …] = {w >> 1 (low, high word),
 // starts before the batch − 1 + (w & 1), 0}, w = the batch's 64 start bits.
 void xtile_phase_tables(const XtileHost &o, std::vector<uint32_t> &bt, std::vector<int32_t> &base_ne);
+// Chunk records of the fp32 iperm reduce (round 11, k_xtile_reduce REC,
+// options.xtile_chunkrec): everything the reduce derived per chunk from the
+// segment table and row_ptr on every call, though it depends on A alone.
+// Chunk c's record is xtile_chunkrec_words(M, S) u32 at c times that many
+// (a multiple of 4: 16-B aligned), copied to LDS as it stands:
+//   bm       M/32 words: bit i set where an owned row starts at chunk position
+//            i < m (the bits the row decode sets from row_ptr);
+//   sbm      M/32 words: bit f set where a non-empty segment starts at flat
+//            position f of the segment concatenation (what the segment scan's
+//            atomicOr sets);
+//   base_ne  S i32: start of the r-th non-empty segment (stream position, or
+//            ring position when o.rdelta is set) − its flat offset, unused
+//            entries repeating the last one (as xtile_phase_tables);
+//   flags    1 word: bit 0 — the row holding position m − 1 runs past the
+//            chunk (row_ptr[cr[c+1]] > ce[c+1]); then zeros up to 16 B.
+// A row without nonzeros has no bit of its own: plans with one keep the
+// row_ptr decode (xtile_policy, csr_has_empty_row).
+inline int64_t xtile_chunkrec_words(int M, int S) { return M / 16 + ((S + 1 + 3) & ~3); }
+void xtile_chunk_records(const XtileHost &o, const void *row_ptr, int rp_bits, std::vector<uint32_t> &rec);
+bool csr_has_empty_row(const void *row_ptr, int rp_bits, int64_t n_rows);
 
 // LDS slot of chunk position i in the XTILE reduce (lhpc_spmv_xtile.hip
 // xt_slot): run t = i/run holds run = 64/elem_bytes elements (64 B) at

@@ -274,6 +274,7 @@ int build_parts(lhpc_spmv_plan *p, const CsrSource &src, int64_t cap, int B) {
     p->part_row.push_back(r0);
     p->part_col.push_back(c0);
     q->xt_acc = acc;
+    if (B > 1) q->opt.xtile_chunkrec = 1;  // column blocks: every block keeps the row_ptr reduce (rows empty in a block)
     LHPC_TRY(xtile_build(q, CsrSource{RowPtrView{lrp.data(), 64}, lc, lv, src.d_rp}));
     p->bytes += q->bytes;
     return LHPC_OK;
@@ -767,7 +768,8 @@ extern "C" int lhpc_spmv_plan_destroy(lhpc_spmv_plan *p) {
                     static_cast<void *>(p->d_seghi), static_cast<void *>(p->d_seg), static_cast<void *>(p->d_pieces), static_cast<void *>(p->d_cont),
                     static_cast<void *>(p->d_col16), static_cast<void *>(p->d_perm), p->d_xg,
                     static_cast<void *>(p->d_pieces_cp), static_cast<void *>(p->d_pext),
-                    static_cast<void *>(p->d_carry), static_cast<void *>(p->d_sell_rp)})
+                    static_cast<void *>(p->d_carry), static_cast<void *>(p->d_sell_rp),
+                    static_cast<void *>(p->d_rec)})
       if (q) (void)hipFree(q);
     if (p->h_scalars) (void)hipHostFree(p->h_scalars);
     for (hipGraphExec_t g : p->cg_graph)
@@ -823,6 +825,34 @@ extern "C" int lhpc_spmv_plan_layout_digest(const lhpc_spmv_plan *p, uint64_t *o
       out[i] = x ^ static_cast<uint64_t>(arr[i].second);
     }
     *n_out = 10;
+    return LHPC_OK;
+  } LHPC_ABI_CATCH
+}
+
+extern "C" int lhpc_spmv_plan_chunkrec(const lhpc_spmv_plan *p, int *on, uint64_t *digest) {
+  try {
+    if (!p || !on) return LHPC_ERR_INVALID_ARG;
+    uint64_t x = 0xcbf29ce484222325ull;
+    *on = 0;
+    if (!p->parts.empty()) {
+      for (const auto *q : p->parts) {
+        int qon = 0;
+        uint64_t qd = 0;
+        LHPC_TRY(lhpc_spmv_plan_chunkrec(q, &qon, digest ? &qd : nullptr));
+        *on |= qon;
+        x = (x ^ qd) * 0x100000001b3ull;
+      }
+    } else if (p->kernel == LHPC_KERNEL_XTILE && p->xt_rec) {
+      *on = 1;
+      if (digest) {
+        LHPC_HIP_TRY(hipSetDevice(p->device));
+        std::vector<unsigned char> h(static_cast<size_t>(p->xt_rec_n) * 4);
+        if (!h.empty()) LHPC_HIP_TRY(hipMemcpy(h.data(), p->d_rec, h.size(), hipMemcpyDeviceToHost));
+        for (unsigned char b : h) x = (x ^ b) * 0x100000001b3ull;
+        x ^= static_cast<uint64_t>(h.size());
+      }
+    }
+    if (digest) *digest = x;
     return LHPC_OK;
   } LHPC_ABI_CATCH
 }

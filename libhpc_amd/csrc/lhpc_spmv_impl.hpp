@@ -87,6 +87,11 @@ struct lhpc_spmv_plan {
   int xt_ring = 0;
   int xt_pre = 0;                         // the reduce reads the plan's phase-A tables (lhpc_options.xtile_pretable)
   int64_t xt_seg_n = 0, xt_seghi_n = 0;  // entries of d_seg / d_seghi
+  // chunk records (lhpc_plan.hpp xtile_chunk_records; lhpc_options.xtile_chunkrec):
+  // xt_rec_n words in d_rec, read by the reduce in place of d_seg / d_seghi / row_ptr
+  uint32_t *d_rec = nullptr;
+  int64_t xt_rec_n = 0;
+  int xt_rec = 0;
   int64_t xt_ring_len = 0;
   int32_t *d_pext = nullptr;
   std::vector<int64_t> xt_hrow;

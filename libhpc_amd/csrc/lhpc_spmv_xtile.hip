@@ -268,7 +268,16 @@ template <typename T> constexpr bool xt_rreg(int G) { return std::is_same<T, flo
 // segments (base_ne, S i32, ring positions) — and the reduce copies them
 // into LDS by LDS-DMA in round trip 1 instead of the segment scan.
 // seg = pbt (u32x4 per batch, as u32), seghi = pbne in that mode.
-template <typename T, int G, int BLK, bool IP, bool AL, bool PRE = false>
+// REC (fp32 iperm, no aligned segments, G = 1, no empty rows, plain y store;
+// round 11): the plan holds one record per chunk (lhpc_plan.hpp
+// xtile_chunk_records: bm, sbm, base_ne, flags) that round trip 1 copies
+// into LDS by LDS-DMA: no segment scan, no row_ptr loads, no atomics, no rpl.
+// Row ends come from bm (position i ends a row when bit i + 1 is set, or at
+// m − 1 unless the flags say the row runs on), the local row index from a
+// popcount prefix over the threads' bm bits; each thread stages the y of the
+// rows that end in its own run, and the block stores them coalesced.  seg =
+// the records in that mode.
+template <typename T, int G, int BLK, bool IP, bool AL, bool PRE = false, bool REC = false>
 __global__ __launch_bounds__(BLK, IP ? LHPC_XT_IP_WAVES : 1) void k_xtile_reduce(
     const int32_t *__restrict__ cdesc, const uint32_t *__restrict__ seg, const int32_t *__restrict__ seghi, int S,
     int64_t hc0, int64_t hrow0, int64_t c0, int64_t C,
@@ -302,14 +311,30 @@ __global__ __launch_bounds__(BLK, IP ? LHPC_XT_IP_WAVES : 1) void k_xtile_reduce
   u32x4 *bt0 = reinterpret_cast<u32x4 *>(xs + M + VW);
   double *ws = reinterpret_cast<double *>(bt0 + (BLK / kWave) * NB);  // per-wave segmented-scan totals
   int *wsf = reinterpret_cast<int *>(ws + BLK / kWave);
+  constexpr int NW = BLK / kWave;
   uint32_t *bm = reinterpret_cast<uint32_t *>(wsf + BLK / kWave);
   uint32_t *sbm = bm + M / 32;
-  constexpr int NW = BLK / kWave;
   uint16_t *rpl = reinterpret_cast<uint16_t *>(sbm + M / 32);  // !RREG: rpl[RMAX + 1]
   uint16_t *rfirst = rpl;                                       // RREG: rfirst[RPT][NW]
   int32_t *rlast = reinterpret_cast<int32_t *>(rfirst + ((RPT * NW + 1) & ~1));
   int32_t *base_ne = RREG ? rlast + 1 : reinterpret_cast<int32_t *>(rpl + ((RMAX + 2) & ~1));
   int32_t *wsum = base_ne + S;
+  // REC (xtile_lds_bytes_g): xs, ws, wsf, wcnt[NW] (row starts per wave), then
+  // the record in its own order — bm[M/32], sbm[M/32], base_ne[S], flags, its
+  // last 64-word DMA row rounded up — then bt.  Everything from sbm on is
+  // dead after phase A and becomes ys[RMAX], the staged y of the chunk's rows.
+  static_assert(!REC || (IP && !AL && !PRE && G == 1 && sizeof(T) == 4), "REC: the fp32 iperm reduce, G = 1");
+  const int RW = M / 16 + ((S + 4) & ~3);  // xtile_chunkrec_words
+  int32_t *wcnt = wsum;
+  if constexpr (REC) {
+    ws = reinterpret_cast<double *>(xs + M + VW);
+    wsf = reinterpret_cast<int *>(ws + NW);
+    wcnt = wsf + NW;
+    bm = reinterpret_cast<uint32_t *>(wcnt + NW);
+    sbm = bm + M / 32;
+    base_ne = reinterpret_cast<int32_t *>(sbm + M / 32);
+    bt0 = reinterpret_cast<u32x4 *>(bm + ((RW + kWave - 1) & ~(kWave - 1)));
+  }
 
   const int tid = threadIdx.x;
   const int lane = tid & (kWave - 1);
@@ -326,7 +351,19 @@ __global__ __launch_bounds__(BLK, IP ? LHPC_XT_IP_WAVES : 1) void k_xtile_reduce
   //      go out while val and row_ptr are still in flight.
   static_assert(!PRE || (IP && !AL), "PRE: the iperm reduce without aligned segments");
   int sa[G], sb[G];
-  if constexpr (PRE) {
+  if constexpr (REC) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    // the record, RW dwords, 64 per wave instruction (the last row's lanes
+    // past the record read 0 through the buffer bound)
+    const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<uint32_t *>(seg + c * RW), 0, RW * 4, 0x00020000);
+    for (int k = wv; k * kWave < RW; k += NW)
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rr, (__attribute__((address_space(3))) void *)(bm + k * kWave), 4,
+                                               (k * kWave + lane) * 4, 0, 0, 0);
+#endif
+    (void)sa;
+    (void)sb;
+  } else if constexpr (PRE) {
 #if defined(__HIP_DEVICE_COMPILE__)
     // the chunk's phase-A tables into LDS: bt (M/64 u32x4 = M/16 dwords,
     // 64 per wave instruction) and base_ne (S dwords, padded to 64 in LDS)
@@ -359,6 +396,10 @@ __global__ __launch_bounds__(BLK, IP ? LHPC_XT_IP_WAVES : 1) void k_xtile_reduce
   const u32x4 d2 = *reinterpret_cast<const u32x4 *>(cdesc + 8 * c + 4);
   const int e0 = static_cast<int>(d[0]), m = static_cast<int>(d[1]) - e0;
   const int r0 = static_cast<int>(d[2]), R = static_cast<int>(d[3]) - r0;
+  // REC: the record's DMA went out with the descriptor loads; waiting for it
+  // here, ahead of the val loads the descriptor addresses, keeps those in
+  // flight across the barrier below
+  if constexpr (REC) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   // val and iperm are stored wave-transposed (lhpc_plan.hpp xtile_wave_pos):
   // in the chunk's wave region w (REG = 64·RUN positions at vbase + w·REG),
   // 16-B vector q of lane l holds that lane's run elements [q·VW, q·VW + VW),
@@ -393,18 +434,28 @@ __global__ __launch_bounds__(BLK, IP ? LHPC_XT_IP_WAVES : 1) void k_xtile_reduce
 #endif
   };
   int rv[RPT];
+  if constexpr (!REC) {
 #pragma unroll
-  for (int q = 0; q < RPT; ++q) {
-    const int j = q * BLK + tid;
-    rv[q] = rp[r0 + (j <= R ? j : R)];
+    for (int q = 0; q < RPT; ++q) {
+      const int j = q * BLK + tid;
+      rv[q] = rp[r0 + (j <= R ? j : R)];
+    }
   }
   // ---- scan: segment ranks / bases and the segment-start bitmap (PRE:
   //      the plan's tables, once their LDS-DMA has landed)
-  if (tid < M / 32) {
-    bm[tid] = 0u;
-    sbm[tid] = 0u;
+  if constexpr (!REC) {
+    if (tid < M / 32) {
+      bm[tid] = 0u;
+      sbm[tid] = 0u;
+    }
   }
-  if constexpr (PRE) {
+  if constexpr (REC) {
+    // a bare barrier: every wave waited for its part of the record above,
+    // and a fence here would drain the val loads
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+  } else if constexpr (PRE) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
   } else {
@@ -606,18 +657,20 @@ __global__ __launch_bounds__(BLK, IP ? LHPC_XT_IP_WAVES : 1) void k_xtile_reduce
   // row_ptr (round trip 2) → local row offsets (registers; a wave's first in
   // rfirst, row R's in rlast) and the row-start bitmap
   int rt[RPT];
+  if constexpr (!REC) {
 #pragma unroll
-  for (int q = 0; q < RPT; ++q) {
-    const int j = q * BLK + tid;
-    rv[q] -= e0;
-    rt[q] = rv[q] <= m ? rv[q] : m + 1;  // > m: continues (rows past R repeat row R's)
-    if constexpr (RREG) {
-      if (lane == 0) rfirst[q * NW + wv] = static_cast<uint16_t>(rt[q]);
-      if (j == R) *rlast = rt[q];
-    } else {
-      if (j <= R) rpl[j] = static_cast<uint16_t>(rt[q]);
+    for (int q = 0; q < RPT; ++q) {
+      const int j = q * BLK + tid;
+      rv[q] -= e0;
+      rt[q] = rv[q] <= m ? rv[q] : m + 1;  // > m: continues (rows past R repeat row R's)
+      if constexpr (RREG) {
+        if (lane == 0) rfirst[q * NW + wv] = static_cast<uint16_t>(rt[q]);
+        if (j == R) *rlast = rt[q];
+      } else {
+        if (j <= R) rpl[j] = static_cast<uint16_t>(rt[q]);
+      }
+      if (j < R && rv[q] < m) atomicOr(bm + (rv[q] >> 5), 1u << (rv[q] & 31));  // empty rows share a bit
     }
-    if (j < R && rv[q] < m) atomicOr(bm + (rv[q] >> 5), 1u << (rv[q] & 31));  // empty rows share a bit
   }
   const int n = m - i0 < RUN ? (m - i0 > 0 ? m - i0 : 0) : RUN;  // valid entries in the run
   if (n < RUN) {  // the chunk's last run (and runs past m): val and x past m → 0 · 0
@@ -672,22 +725,32 @@ __global__ __launch_bounds__(BLK, IP ? LHPC_XT_IP_WAVES : 1) void k_xtile_reduce
 #pragma unroll
   for (int q = 0; q < NV; ++q) xr[q ^ swz] = xq[q];
   const bool has_head = n > 0 && !(mask & 1u);
-  const bool cont = (RREG ? *rlast : static_cast<int>(rpl[R])) > m;  // the row active at m−1 runs past the chunk
+  bool cont;  // the row active at m−1 runs past the chunk
+  if constexpr (REC) cont = (base_ne[S] & 1) != 0;
+  else cont = (RREG ? *rlast : static_cast<int>(rpl[R])) > m;
   // ---- rows that cross runs: segmented scan over threads (run order) of
   //      x(t) = tail piece if run t holds a row start, else its whole-run sum;
   //      the row open when run t begins is the exclusive value S(t−1)
   bool fl = n > 0 && mask != 0u;
   double sv = wave_seg_scan(fl ? acc : hsave, fl);
+  // REC: row starts at or before the end of this thread's run, in the wave
+  int cnt = 0, cincl = 0;
+  if constexpr (REC) {
+    cnt = __popc(mask);
+    cincl = wave_incl_scan(cnt);
+  }
   if (lane == kWave - 1) {
     ws[wv] = sv;
     wsf[wv] = fl ? 1 : 0;
+    if constexpr (REC) wcnt[wv] = cincl;
   }
   __syncthreads();
   double cw = 0.0;  // segmented carry of the waves before this one
-  int gw = 0;
+  int gw = 0, rowbase = cincl - cnt;  // REC: row starts before this thread's run
   for (int w = 0; w < wv; ++w) {
     cw = wsf[w] ? ws[w] : cw + ws[w];
     gw |= wsf[w];
+    if constexpr (REC) rowbase += wcnt[w];
   }
   LHPC_XT_STAMP(6, 0)
   if (!fl) sv = cw + sv;
@@ -696,7 +759,10 @@ __global__ __launch_bounds__(BLK, IP ? LHPC_XT_IP_WAVES : 1) void k_xtile_reduce
   const double oin = dpp_f64_old<kShr1>(cw, sv);                                 // S(t−1)
   const int fin = __builtin_amdgcn_update_dpp(gw, fin_incl, kShr1, 0xF, 0xF, false);  // starts before run t
   const int tlast = m > 0 ? (m - 1) / RUN : -1;
-  if (tid == 0 && !(m > 0 && (RREG ? rt[0] : static_cast<int>(rpl[0])) > 0)) carry[2 * c] = 0.0;  // no head piece
+  bool head;  // the chunk begins inside a row of the chunk before it
+  if constexpr (REC) head = m > 0 && !(bm[0] & 1u);
+  else head = m > 0 && (RREG ? rt[0] : static_cast<int>(rpl[0])) > 0;
+  if (tid == 0 && !head) carry[2 * c] = 0.0;  // no head piece
   if (has_head) {
     const int i1 = i0 + n;
     const bool end_i1 = i1 < m ? ((bm[i1 >> 5] >> (i1 & 31)) & 1u) != 0 : !cont;
@@ -713,6 +779,38 @@ __global__ __launch_bounds__(BLK, IP ? LHPC_XT_IP_WAVES : 1) void k_xtile_reduce
     }
   }
   if (tid == tlast && mask && cont) carry[2 * c + 1] = acc;  // own tail row continues
+  if constexpr (REC) {
+    // y of the rows that end in this thread's run, from their last positions:
+    // slots this thread wrote itself (the run above, the head's sum), so no
+    // barrier before reading them.  The r-th end of the run is row (starts at
+    // or before it) − 1; −1 is the row of the chunk before (its piece went to
+    // carry).  The values are staged by row in ys (LDS dead since phase A)
+    // and stored coalesced after one barrier: every owned row but a last one
+    // that runs on ends in the chunk (no empty rows).  (Storing them straight
+    // from the runs, without the barrier, takes as many store rounds as the
+    // fullest run has row ends: C2 the same, C4 reduce 88.2 → 91.5 µs.)
+    LHPC_XT_STAMP(7, 0)
+    LHPC_DEVICE_CHECK(!y_add);
+    T *ys = reinterpret_cast<T *>(sbm);
+    if (n > 0) {
+      const int i1 = i0 + n;
+      const bool end_i1 = i1 < m ? ((bm[i1 >> 5] >> (i1 & 31)) & 1u) != 0 : !cont;
+      uint32_t em = (mask >> 1) | (end_i1 ? 1u << (n - 1) : 0u);  // row ends of the run
+      int jr = em ? rowbase - 1 + __popc(mask & ((2u << __builtin_ctz(em)) - 1u)) : 0;
+      while (em) {
+        const int k = __builtin_ctz(em);
+        em &= em - 1u;
+        if (jr >= 0 && jr < R) ys[jr] = xs[xt_slot<T>(i0 + k)];
+        ++jr;
+      }
+    }
+    __syncthreads();
+    const int nst = R - (cont ? 1 : 0);
+    for (int j = tid; j < nst; j += BLK) y[r0 + j] = ys[j];
+    LHPC_XT_STAMP(8, 0)
+    LHPC_XT_STAMP(9, 1)
+    return;
+  }
   __syncthreads();
   LHPC_XT_STAMP(7, 0)
   // coalesced y store of the owned rows from their last positions (a row
@@ -775,9 +873,14 @@ __global__ __launch_bounds__(kXtFixBlock) void k_xtile_fixup(
 // form spilled and could never be selected)
 template <typename T> constexpr int xt_gmax() { return 4096 / xt_red_blk<T>(); }
 template <typename T>
-size_t xtile_lds_bytes_g(int S, int g, bool pre = false) {
+size_t xtile_lds_bytes_g(int S, int g, bool pre = false, bool rec = false) {
   constexpr int BLK = xt_red_blk<T>(), M = XtRed<T, BLK>::M, RMAX = XtRed<T, BLK>::Rmax, W = BLK / kWave;
   constexpr int RPT = (RMAX + 1 + BLK - 1) / BLK;
+  if (rec) {  // xs, ws + wsf + wcnt, bm, then sbm … bt: the record's DMA rows and bt, at least ys[RMAX]
+    const size_t rw64 = static_cast<size_t>((xtile_chunkrec_words(M, S) + kWave - 1) / kWave * kWave) * 4;
+    return static_cast<size_t>(M + 16 / sizeof(T)) * sizeof(T) + W * (sizeof(double) + 8) + M / 32 * sizeof(uint32_t) +
+           std::max<size_t>(RMAX * sizeof(T), rw64 - M / 32 * sizeof(uint32_t) + W * xt_run<T>() * 16);
+  }
   const size_t rows = xt_rreg<T>(g) ? ((RPT * W + 1) & ~1) * sizeof(uint16_t) + sizeof(int32_t)  // rfirst, rlast
                                     : ((RMAX + 2) & ~1) * sizeof(uint16_t);                     // rpl
   return static_cast<size_t>(M + 16 / sizeof(T)) * sizeof(T) + W * xt_run<T>() * 16 + W * (sizeof(double) + 4) +
@@ -815,7 +918,15 @@ const void *xtile_reduce_fn(int g) {
 // ip: iperm reduce; al: aligned segments (iperm only, else nullptr); pre:
 // the plan's phase-A tables instead of the segment scan (iperm, not aligned)
 template <typename T>
-const void *xtile_reduce_fn(int g, bool ip, bool al, bool pre = false) {
+const void *xtile_reduce_fn(int g, bool ip, bool al, bool pre = false, bool rec = false) {
+  if (rec) {  // fp32 only (xtile_policy)
+    if constexpr (sizeof(T) == 4)
+      return ip && !al && !pre && g == 1
+                 ? reinterpret_cast<const void *>(k_xtile_reduce<T, 1, xt_red_blk<T>(), true, false, false, true>)
+                 : nullptr;
+    else
+      return nullptr;
+  }
   if (pre) return ip && !al && g == 1 ? xtile_reduce_fn<T, 1, true, false, true>() : nullptr;  // G = 2 spilled
   if (al) return ip ? xtile_reduce_fn<T, true, true>(g) : nullptr;
   return ip ? xtile_reduce_fn<T, true, false>(g) : xtile_reduce_fn<T, false, false>(g);
@@ -878,9 +989,9 @@ int launch_reduce(const lhpc_spmv_plan *p, int64_t c0, int64_t c1, int64_t n0, i
   if (c1 > c0) {
     const int64_t Cx = (c1 - c0 + 7) / 8;
     const dim3 rg(static_cast<unsigned>(8 * Cx)), rb(xt_red_blk<T>());
-    const void *fn = xtile_reduce_fn<T>(xtile_g<T>(p->S), p->xt_p == 3, p->xt_al != 0, p->xt_pre != 0);
+    const void *fn = xtile_reduce_fn<T>(xtile_g<T>(p->S), p->xt_p == 3, p->xt_al != 0, p->xt_pre != 0, p->xt_rec != 0);
     const int32_t *cd = p->d_cdesc, *sh = p->d_seghi, *rp = static_cast<const int32_t *>(p->d_row_ptr);
-    const uint32_t *so = p->d_seg;
+    const uint32_t *so = p->xt_rec ? p->d_rec : p->d_seg;  // chunk records in the segment table's place
     int S = p->S, total = static_cast<int>(ring >= 0 ? p->xt_ring_len : p->xt_total);
     int64_t hc0 = ring >= 0 ? c0 : 0, hrow0 = ring >= 0 ? p->xt_hrow[static_cast<size_t>(ring)] : 0;
     const T *xg = static_cast<const T *>(p->d_xg), *val = static_cast<const T *>(p->d_val);
@@ -1233,11 +1344,12 @@ struct XtBuild {
     p->xt_pre = pol.pre ? 1 : 0;
     p->xt_u = pol.steps;
     p->xt_nt = pol.nt(p->xt_mall) ? 1 : 0;
-    p->xt_lds = xtile_lds_bytes_g<T>(xt.S, xtile_g<T>(xt.S), pol.pre);
+    p->xt_rec = pol.rec ? 1 : 0;
+    p->xt_lds = xtile_lds_bytes_g<T>(xt.S, xtile_g<T>(xt.S), pol.pre, pol.rec);
 #ifdef LHPC_XT_LDS_TOTAL  // A/B build only: reduce blocks padded to this many bytes of LDS (fewer per CU)
     if (sizeof(T) == 4) p->xt_lds = std::max<size_t>(p->xt_lds, LHPC_XT_LDS_TOTAL);
 #endif
-    const void *rfn = xtile_reduce_fn<T>(xtile_g<T>(xt.S), pol.iperm, pol.aligned, pol.pre);
+    const void *rfn = xtile_reduce_fn<T>(xtile_g<T>(xt.S), pol.iperm, pol.aligned, pol.pre, pol.rec);
     if (!rfn) return LHPC_ERR_UNSUPPORTED;  // more tiles than the reduce's segment table holds
     LHPC_HIP_TRY(hipFuncSetAttribute(rfn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(p->xt_lds)));
     std::vector<int32_t> rp32(static_cast<size_t>(n_rows + 1));
@@ -1264,6 +1376,12 @@ struct XtBuild {
       LHPC_TRY(up(&p->d_seghi, seghi.data(), seghi.size() * 4));
       p->xt_seg_n = static_cast<int64_t>(seg.size());
       p->xt_seghi_n = static_cast<int64_t>(seghi.size());
+    }
+    if (pol.rec) {  // beside the segment table, which lhpc_spmv_plan_layout_digest still covers
+      std::vector<uint32_t> rec;
+      xtile_chunk_records(xt, rp.p, rp.bits, rec);
+      LHPC_TRY(up(&p->d_rec, rec.data(), rec.size() * 4));
+      p->xt_rec_n = static_cast<int64_t>(rec.size());
     }
     LHPC_TRY(up(&p->d_xg, nullptr, static_cast<size_t>((p->xt_ring ? xt.ring_len : xt.total) + 2) * tsz));
     LHPC_TRY(up(&p->d_carry, nullptr, static_cast<size_t>(2 * C + 2) * 8));
@@ -1299,6 +1417,10 @@ int build_t(lhpc_spmv_plan *p, RowPtrView rp, const int32_t *col_idx, const void
   sh.W = xtile_tile_width(sh.n_cols, sizeof(T), sh.cus, tw ? std::atoi(tw) != 0 : -1);
   const int64_t tiles = (sh.n_cols + sh.W - 1) / sh.W;
   sh.G = xtile_g<T>(static_cast<int>(std::min<int64_t>(tiles, kXtMaxTiles)));
+  sh.y_add = p->xt_acc != 0;
+  // read by the policy only where chunk records could be chosen
+  if (sizeof(T) == 4 && sh.G == 1 && !sh.y_add && p->opt.xtile_chunkrec != 1)
+    sh.empty_rows = csr_has_empty_row(rp.p, rp.bits, p->n_rows);
   const XtilePolicy pol = xtile_policy(sh, p->opt);
   p->xt_p = pol.iperm ? 3 : 1;
   p->xt_al = pol.aligned ? 1 : 0;
