@@ -83,7 +83,24 @@ enum lhpc_plan_flags {
   LHPC_PLAN_FAST_PARTIALS = 1u << 7,
   LHPC_PLAN_EXACT_PARTIALS = 1u << 8,
   LHPC_PLAN_FORCE_XTILE = 1u << 9,
-  LHPC_PLAN_FORCE_SELL = 1u << 10  /* LHPC_ERR_UNSUPPORTED past 8 nonzeros per row */
+  LHPC_PLAN_FORCE_SELL = 1u << 10, /* LHPC_ERR_UNSUPPORTED past 8 nonzeros per row */
+  /* The plan is the plan of Aᵀ: the caller passes A (n_rows × n_cols) as
+   * always, lhpc_spmv reads an x of n_rows and writes a y of n_cols (lhpc_spmm
+   * likewise), plan info reports the operator's shape (n_rows = A's n_cols).
+   * Host input is uploaded, A is transposed on the plan's device
+   * (lhpc_csr_transpose below, which validates it: LHPC_ERR_BAD_CSR) and the
+   * build goes on as from LHPC_PLAN_DEVICE_INPUT with Aᵀ's arrays, which are
+   * freed once the layout stands.  The plan is indistinguishable from one
+   * built, with the same other flags and options, from the arrays
+   * lhpc_csr_transpose returns for A: the same kernel family, layout digests,
+   * plan info except device_bytes, and bits from every call that takes it.
+   * It keeps the permutation (4 B per entry, in device_bytes) so that
+   * lhpc_spmv_plan_set_values / lhpc_spmm_plan_set_values take the values in
+   * A's CSR order (see there).  n_rows > INT32_MAX: LHPC_ERR_INVALID_ARG.
+   * LHPC_ERR_UNSUPPORTED before any device work: with n_splits > 0, with a
+   * multi-device plan (n_devices > 1 or options.multi_force), and in
+   * lhpc_dist_spmv_plan_create*.                                            */
+  LHPC_PLAN_TRANSPOSE = 1u << 11
 };
 
 /* kernel families a plan can select (lhpc_spmv_plan_info.kernel)          */
@@ -328,8 +345,15 @@ int lhpc_spmv_plan_chunkrec(const lhpc_spmv_plan *plan, int *on, uint64_t *diges
  *       n_rows + 1 row offsets from the layout on the device and keeps them
  *       with the plan (int64, counted in device_bytes from then on) — that
  *       one call allocates and synchronises the stream; every later call is
- *       one kernel launch.
- *   otherwise               val is a host pointer: the values pass through
+ *       one kernel launch.  Likewise a LHPC_PLAN_TRANSPOSE plan: `val` is in
+ *       the CSR order of A, the matrix the caller passed (not of Aᵀ); it is
+ *       gathered through the plan's permutation into a plan-owned buffer of
+ *       nnz values and the family's update runs from there.  The first update
+ *       allocates that buffer (counted in device_bytes from then on) and
+ *       synchronises the stream; every later call is launches and
+ *       asynchronous copies only.  Afterwards the plan equals a fresh
+ *       LHPC_PLAN_TRANSPOSE plan of A with the new values.
+ *   otherwise              val is a host pointer: the values pass through
  *       library scratch in HBM where they are re-ordered (XTILE, SELL) or are
  *       copied straight into place, and the stream is synchronised before
  *       return.
@@ -431,9 +455,10 @@ int lhpc_csr_partition_rows(const void *row_ptr, int row_ptr_bits,
  *   dtype, row_ptr, row_ptr_bits, col_idx, val   as lhpc_spmv_plan_create
  *   device   HIP device ordinal; -1 = current device
  *   flags    LHPC_PLAN_VALIDATE (implied: A is always checked,
- *            LHPC_ERR_BAD_CSR) and LHPC_PLAN_DEVICE_INPUT (the arrays are on
+ *            LHPC_ERR_BAD_CSR), LHPC_PLAN_DEVICE_INPUT (the arrays are on
  *            the plan's device: validated there, copied device to device;
- *            only row_ptr comes to the host, for the block table).  Any
+ *            only row_ptr comes to the host, for the block table) and
+ *            LHPC_PLAN_TRANSPOSE (Y = Aᵀ·X, see the flag).  Any
  *            LHPC_PLAN_FORCE_* or *_PARTIALS flag: LHPC_ERR_INVALID_ARG.
  * Null pointers, bad dtype / row_ptr_bits and negative sizes are
  * LHPC_ERR_INVALID_ARG before any device is touched; no gfx950 device is
@@ -503,7 +528,9 @@ int lhpc_spmm_dot(lhpc_spmm_plan *plan, int k, const void *X, int64_t ldx, void 
  * CSR order: one asynchronous copy on `stream` (device values: nothing else,
  * capturable; host values: the stream is synchronised before return).
  * LHPC_ERR_INVALID_ARG as there; LHPC_ERR_BUSY while a lhpc_cg_solve_multi
- * holds the plan.
+ * holds the plan.  A LHPC_PLAN_TRANSPOSE plan takes the values in A's CSR
+ * order and gathers them through its permutation first, as described there
+ * (the first update allocates the nnz-value buffer and synchronises).
  */
 int lhpc_spmm_plan_set_values(lhpc_spmm_plan *plan, const void *val, int64_t nnz,
                               int values_on_device, void *stream);
@@ -633,6 +660,51 @@ int lhpc_coo_to_csr(int dtype, int64_t n_rows, int64_t n_cols, int64_t nnz,
                     void *row_ptr, int row_ptr_bits, int32_t *col_out,
                     void *val_out, int64_t *nnz_out, int on_device,
                     void *stream);
+
+/* -------------------------------------------------------- CSR transpose
+ * The CSR of Aᵀ (n_cols × n_rows) from the CSR of A (n_rows × n_cols), on the
+ * GPU.  The reference has no counterpart (it has no SpMV).  A as
+ * for lhpc_spmv_plan_create; the outputs are
+ *   t_row_ptr  n_cols + 1 offsets in the same row_ptr_bits width
+ *   t_col_idx  nnz former row indices
+ *   t_val      nnz values of dtype
+ *   perm       the permutation of 0 … nnz−1 that a STABLE sort of the entry
+ *              positions by col_idx produces: output position q holds input
+ *              entry perm[q].  In numpy terms
+ *                perm         = np.argsort(col_idx, kind="stable")
+ *                t_col_idx[q] = the row of entry perm[q]
+ *                t_val[q]     = val[perm[q]]
+ *                t_row_ptr[c] = #{p : col_idx[p] < c}
+ * Nothing is left to choice, so every output array is defined bit for bit.
+ * Hence: within a row of Aᵀ the column indices ascend, whatever the order
+ * inside A's rows; duplicate coordinates are kept, in input order, not merged
+ * (lhpc_coo_to_csr merges); the transpose of the transpose of a CSR with
+ * sorted rows is that CSR.
+ * val and t_val may both be NULL (pattern only); perm may be NULL.  The output
+ * arrays must not overlap the input arrays.
+ * on_device as for the sort: 1, every array is an HBM pointer on the current
+ * device, scratch (3 words per entry beside the sort's) comes from the
+ * library's stream-ordered pool and the work is issued on `stream`; 0, host
+ * arrays staged through HBM.  Either way A is validated on the device first
+ * (monotone row_ptr, row_ptr[n_rows] = nnz, columns in range) and the call
+ * returns only after `stream` has drained: a plan-build-time operation, like
+ * lhpc_coo_to_csr.  The work is a stable 32-bit pair sort of (col_idx,
+ * position) over the bits that hold n_cols − 1 and one pass that gathers the
+ * rows and values and writes t_row_ptr at the key boundaries: integer work
+ * only, no atomics, bit-reproducible.
+ * Argument checks come first, before any device is touched:
+ *   LHPC_ERR_INVALID_ARG   NULL row_ptr / t_row_ptr, NULL col_idx / t_col_idx
+ *       with nnz > 0, only one of val / t_val NULL, bad dtype or
+ *       row_ptr_bits, a negative size, n_rows or n_cols above INT32_MAX,
+ *       nnz > INT32_MAX with 32-bit offsets
+ *   LHPC_ERR_UNSUPPORTED   nnz ≥ 2^32 (the sort's limit)
+ * then LHPC_ERR_BAD_CSR for an invalid A (nothing is promised about the
+ * outputs then).  nnz = 0: t_row_ptr all zeros, LHPC_OK.
+ */
+int lhpc_csr_transpose(int dtype, int64_t n_rows, int64_t n_cols, int64_t nnz,
+                       const void *row_ptr, int row_ptr_bits, const int32_t *col_idx,
+                       const void *val, void *t_row_ptr, int32_t *t_col_idx, void *t_val,
+                       uint32_t *perm, int on_device, void *stream);
 
 /* ------------------------------------------------------------------- CG
  * Conjugate gradient on an SpMV plan (no reference

@@ -40,6 +40,7 @@ class SpMMPlan {
   template <typename OffsetT>
   explicit SpMMPlan(const CSRMatrix<T, std::int32_t, OffsetT> &A, int device = -1, unsigned flags = LHPC_PLAN_DEFAULT)
       : n_rows_(A.n_rows), n_cols_(A.n_cols) {
+    transposed(flags);
     lhpc::checkLhpc(lhpc_spmm_plan_create(&plan_, std::is_same_v<T, float> ? LHPC_F32 : LHPC_F64, A.n_rows, A.n_cols,
                                           A.nnz(), A.row_ptr.data(), sizeof(OffsetT) * 8, A.col_idx.data(),
                                           A.val.data(), device, flags));
@@ -47,6 +48,7 @@ class SpMMPlan {
   // A already in HBM (sparse/DeviceCSR.hpp): validated and copied on the device
   explicit SpMMPlan(const DeviceCSRView<T> &A, unsigned flags = LHPC_PLAN_DEFAULT)
       : n_rows_(A.n_rows), n_cols_(A.n_cols) {
+    transposed(flags);
     lhpc::checkLhpc(lhpc_spmm_plan_create(&plan_, std::is_same_v<T, float> ? LHPC_F32 : LHPC_F64, A.n_rows, A.n_cols,
                                           A.nnz, A.row_ptr, A.row_ptr_bits, A.col_idx, A.val, A.device,
                                           flags | LHPC_PLAN_DEVICE_INPUT));
@@ -54,13 +56,14 @@ class SpMMPlan {
   SpMMPlan(const SpMMPlan &) = delete;
   SpMMPlan &operator=(const SpMMPlan &) = delete;
   SpMMPlan(SpMMPlan &&o) noexcept
-      : plan_(std::exchange(o.plan_, nullptr)), n_rows_(o.n_rows_), n_cols_(o.n_cols_) {}
+      : plan_(std::exchange(o.plan_, nullptr)), n_rows_(o.n_rows_), n_cols_(o.n_cols_), transposed_(o.transposed_) {}
   SpMMPlan &operator=(SpMMPlan &&o) noexcept {
     if (this != &o) {
       reset();
       plan_ = std::exchange(o.plan_, nullptr);
       n_rows_ = o.n_rows_;
       n_cols_ = o.n_cols_;
+      transposed_ = o.transposed_;
     }
     return *this;
   }
@@ -78,11 +81,14 @@ class SpMMPlan {
   }
   template <typename OffsetT>
   void set_values(const CSRMatrix<T, std::int32_t, OffsetT> &A) {
-    if (A.n_rows != n_rows_ || A.n_cols != n_cols_) lhpc::throwLhpcError(LHPC_ERR_INVALID_ARG, __FILE__, __LINE__);
+    // a LHPC_PLAN_TRANSPOSE plan: A's shape (and CSR order), not the operator's
+    if (A.n_rows != (transposed_ ? n_cols_ : n_rows_) || A.n_cols != (transposed_ ? n_rows_ : n_cols_))
+      lhpc::throwLhpcError(LHPC_ERR_INVALID_ARG, __FILE__, __LINE__);
     set_values(A.val.data(), static_cast<std::int64_t>(A.nnz()));
   }
   std::int64_t rows() const noexcept { return n_rows_; }
   std::int64_t cols() const noexcept { return n_cols_; }
+  bool is_transposed() const noexcept { return transposed_; }
   lhpc_spmm_plan *native() noexcept { return plan_; }
 
  private:
@@ -90,8 +96,14 @@ class SpMMPlan {
     if (plan_) lhpc_spmm_plan_destroy(plan_);
     plan_ = nullptr;
   }
+  // LHPC_PLAN_TRANSPOSE: the plan is Aᵀ's, rows() and cols() the operator's
+  void transposed(unsigned flags) noexcept {
+    transposed_ = (flags & LHPC_PLAN_TRANSPOSE) != 0;
+    if (transposed_) std::swap(n_rows_, n_cols_);
+  }
   lhpc_spmm_plan *plan_ = nullptr;
   std::int64_t n_rows_ = 0, n_cols_ = 0;
+  bool transposed_ = false;
 };
 
 // Host blocks: the logical cells [0, n) × [0, k) of 2-D flat arrays.  The

@@ -58,6 +58,7 @@ class SpMVPlan {
   SpMVPlan(const CSRMatrix<T, std::int32_t, OffsetT> &A, const std::vector<int> &devices,
            unsigned flags = LHPC_PLAN_DEFAULT, const lhpc_options *opts = nullptr)
       : n_rows_(A.n_rows), n_cols_(A.n_cols), n_devices_(static_cast<int>(devices.size())) {
+    transposed(flags);
     lhpc::checkLhpc(lhpc_spmv_plan_create_opts(&plan_, std::is_same_v<T, float> ? LHPC_F32 : LHPC_F64, A.n_rows,
                                                A.n_cols, A.nnz(), A.row_ptr.data(), sizeof(OffsetT) * 8,
                                                A.col_idx.data(), A.val.data(), devices.data(),
@@ -66,6 +67,7 @@ class SpMVPlan {
   explicit SpMVPlan(const DeviceCSRView<T> &A, unsigned flags = LHPC_PLAN_DEFAULT,
                     const lhpc_options *opts = nullptr)
       : n_rows_(A.n_rows), n_cols_(A.n_cols) {
+    transposed(flags);
     const int dev[1] = {A.device};
     lhpc::checkLhpc(lhpc_spmv_plan_create_opts(&plan_, std::is_same_v<T, float> ? LHPC_F32 : LHPC_F64, A.n_rows,
                                                A.n_cols, A.nnz, A.row_ptr, A.row_ptr_bits, A.col_idx, A.val, dev, 1,
@@ -75,6 +77,7 @@ class SpMVPlan {
   explicit SpMVPlan(const CSRMatrix<T, std::int32_t, OffsetT> &A, int device = -1,
                     unsigned flags = LHPC_PLAN_DEFAULT, const lhpc_options *opts = nullptr)
       : n_rows_(A.n_rows), n_cols_(A.n_cols) {
+    transposed(flags);
     const int dev[1] = {device};
     lhpc::checkLhpc(lhpc_spmv_plan_create_opts(&plan_, std::is_same_v<T, float> ? LHPC_F32 : LHPC_F64,
                                                A.n_rows, A.n_cols, A.nnz(), A.row_ptr.data(),
@@ -85,7 +88,8 @@ class SpMVPlan {
   SpMVPlan(const SpMVPlan &) = delete;
   SpMVPlan &operator=(const SpMVPlan &) = delete;
   SpMVPlan(SpMVPlan &&o) noexcept
-      : plan_(std::exchange(o.plan_, nullptr)), n_rows_(o.n_rows_), n_cols_(o.n_cols_), n_devices_(o.n_devices_) {}
+      : plan_(std::exchange(o.plan_, nullptr)), n_rows_(o.n_rows_), n_cols_(o.n_cols_), n_devices_(o.n_devices_),
+        transposed_(o.transposed_) {}
   SpMVPlan &operator=(SpMVPlan &&o) noexcept {
     if (this != &o) {
       reset();
@@ -93,6 +97,7 @@ class SpMVPlan {
       n_rows_ = o.n_rows_;
       n_cols_ = o.n_cols_;
       n_devices_ = o.n_devices_;
+      transposed_ = o.transposed_;
     }
     return *this;
   }
@@ -111,14 +116,20 @@ class SpMVPlan {
   void set_values(const T *val, std::int64_t nnz, bool on_device = false, void *stream = nullptr) {
     lhpc::checkLhpc(lhpc_spmv_plan_set_values(plan_, val, nnz, on_device ? 1 : 0, stream));
   }
-  // … from a host matrix of the plan's shape and structure (only A.val is read)
+  // A plan built with LHPC_PLAN_TRANSPOSE takes the values in the CSR order of
+  // A, the matrix it was built from.
+  // … from a host matrix of the shape and structure the plan was built from
+  // (a transposed plan: A's shape, not the operator's; only A.val is read)
   template <typename OffsetT>
   void set_values(const CSRMatrix<T, std::int32_t, OffsetT> &A) {
-    if (A.n_rows != n_rows_ || A.n_cols != n_cols_) lhpc::throwLhpcError(LHPC_ERR_INVALID_ARG, __FILE__, __LINE__);
+    if (A.n_rows != (transposed_ ? n_cols_ : n_rows_) || A.n_cols != (transposed_ ? n_rows_ : n_cols_))
+      lhpc::throwLhpcError(LHPC_ERR_INVALID_ARG, __FILE__, __LINE__);
     set_values(A.val.data(), static_cast<std::int64_t>(A.nnz()));
   }
+  // the operator's shape: with LHPC_PLAN_TRANSPOSE rows() is A's n_cols
   std::int64_t rows() const noexcept { return n_rows_; }
   std::int64_t cols() const noexcept { return n_cols_; }
+  bool is_transposed() const noexcept { return transposed_; }
   int devices() const noexcept { return n_devices_; }
   lhpc_spmv_plan *native() noexcept { return plan_; }
 
@@ -127,9 +138,15 @@ class SpMVPlan {
     if (plan_) lhpc_spmv_plan_destroy(plan_);
     plan_ = nullptr;
   }
+  // LHPC_PLAN_TRANSPOSE: the plan is Aᵀ's, rows() and cols() the operator's
+  void transposed(unsigned flags) noexcept {
+    transposed_ = (flags & LHPC_PLAN_TRANSPOSE) != 0;
+    if (transposed_) std::swap(n_rows_, n_cols_);
+  }
   lhpc_spmv_plan *plan_ = nullptr;
   std::int64_t n_rows_ = 0, n_cols_ = 0;
   int n_devices_ = 1;
+  bool transposed_ = false;
 };
 
 // Host vectors: the logical cells [0, n) of 1-D flat arrays (ghost cells, if

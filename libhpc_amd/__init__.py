@@ -29,7 +29,7 @@ __all__ = [
     "csr_partition_rows", "blur_x", "blur_y", "stencil7", "stencil7_planes",
     "gen_uniform_csr", "gen_powerlaw_csr", "gen_values", "padded_shape",
     "PLAN_VALIDATE", "PLAN_FORCE_ROWGROUP", "PLAN_FORCE_ADAPTIVE", "PLAN_FORCE_XSLICE", "PLAN_FAST_PARTIALS", "PLAN_EXACT_PARTIALS",
-    "PLAN_FORCE_XTILE", "PLAN_FORCE_SELL", "KERNEL_XTILE", "KERNEL_SELL",
+    "PLAN_FORCE_XTILE", "PLAN_FORCE_SELL", "PLAN_TRANSPOSE", "csr_transpose", "KERNEL_XTILE", "KERNEL_SELL",
     "KERNEL_ROWGROUP", "KERNEL_ADAPTIVE", "KERNEL_XSLICE",
 ]
 
@@ -47,6 +47,7 @@ PLAN_FAST_PARTIALS = 1 << 7
 PLAN_EXACT_PARTIALS = 1 << 8
 PLAN_FORCE_XTILE = 1 << 9
 PLAN_FORCE_SELL = 1 << 10
+PLAN_TRANSPOSE = 1 << 11
 KERNEL_ROWGROUP, KERNEL_ADAPTIVE, KERNEL_XSLICE, KERNEL_XTILE, KERNEL_SELL = 0, 1, 2, 3, 4
 
 # every symbol include/lhpc.h declares (checked by tests/test_abi.py)
@@ -76,6 +77,7 @@ ABI_SYMBOLS = (
     "lhpc_spmm_dot", "lhpc_cg_solve_multi",
     "lhpc_spmv_plan_set_values", "lhpc_spmm_plan_set_values",
     "lhpc_spmv_plan_chunkrec",
+    "lhpc_csr_transpose",
 )
 
 if not os.path.exists(LIB_PATH):
@@ -240,6 +242,7 @@ _sig("lhpc_radix_sort_pairs_u64", _i, _p, _p, _i64, _i, _i, _i, _p)
 _sig("lhpc_scratch_trim", _i, _i)
 _sig("lhpc_scratch_poison", _i, _i64, _i, _p)
 _sig("lhpc_coo_to_csr", _i, _i, _i64, _i64, _i64, _p, _p, _p, _p, _i, _p, _p, C.POINTER(_i64), _i, _p)
+_sig("lhpc_csr_transpose", _i, _i, _i64, _i64, _i64, _p, _i, _p, _p, _p, _p, _p, _p, _i, _p)
 _sig("lhpc_cg_solve", _i, _p, _p, _p, _d, _i, _i, C.POINTER(_i), C.POINTER(_d), _p)
 _sig("lhpc_vec_dot", _i, _i, _i64, _p, _p, _p, _p)
 _sig("lhpc_spmv_dot", _i, _p, _p, _p, _p, _p, _p)
@@ -405,7 +408,7 @@ class SpMVPlan:
     """
 
     def __init__(self, row_ptr, col_idx, val, n_cols: int, flags: int = 0,
-                 device: Optional[int] = None, splits=None, options=None, devices=None):
+                 device: Optional[int] = None, splits=None, options=None, devices=None, transpose: bool = False):
         """``splits``: ascending rows in (0, n_rows); the plan is then a
         row-range plan (lhpc_spmv_plan_create_split: stage(x) once, then
         range(k, y_k) per range) and raises LhpcError (LHPC_ERR_UNSUPPORTED)
@@ -414,8 +417,14 @@ class SpMVPlan:
         (lhpc_spmv_plan_create_opts).  ``devices``: a list of HIP device
         ordinals for a single-process multi-device plan (a
         device may repeat: several shares of one GPU); ``plan(x, y)`` then
-        takes x, y on devices[0] and ``plan.multi(xs, ys)`` full replicas."""
+        takes x, y on devices[0] and ``plan.multi(xs, ys)`` full replicas.
+        ``transpose`` (LHPC_PLAN_TRANSPOSE): the arrays are A's (n_rows ×
+        ``n_cols``) and the plan is Aᵀ's: ``plan(x)`` takes n_rows values and
+        gives n_cols, ``plan.n_rows`` / ``plan.n_cols`` are the operator's, and
+        ``set_values`` takes the values in A's CSR order."""
         a = _csr_arrays(row_ptr, col_idx, val)
+        if transpose:
+            flags |= PLAN_TRANSPOSE
         if a.device is not None:
             # device-resident CSR (LHPC_PLAN_DEVICE_INPUT): validated and, for
             # XTILE, laid out on the GPU; the tensors must live on the plan's device
@@ -425,8 +434,10 @@ class SpMVPlan:
             self._dev_arrays = a.keep
         self.dtype, self.np_dtype = a.dtype, a.np_dtype
         rp_ptr, rp_bits, col_ptr, val_ptr = a.rp_ptr, a.rp_bits, a.col_ptr, a.val_ptr
-        self.n_rows = a.n_rows
-        self.n_cols = int(n_cols)
+        # the operator's shape (a transposed plan's rows are A's columns); a_rows × a_cols is A's
+        a_rows, a_cols = a.n_rows, int(n_cols)
+        self.transposed = bool(flags & PLAN_TRANSPOSE)
+        self.n_rows, self.n_cols = (a_cols, a_rows) if self.transposed else (a_rows, a_cols)
         self.nnz = a.nnz
         self._h = _p()
         if devices is not None:
@@ -441,13 +452,13 @@ class SpMVPlan:
         if splits is None and options is None:
             self.splits = None
             _check(lib.lhpc_spmv_plan_create(
-                C.byref(self._h), self.dtype, self.n_rows, self.n_cols, self.nnz,
+                C.byref(self._h), self.dtype, a_rows, a_cols, self.nnz,
                 rp_ptr, rp_bits, col_ptr, val_ptr, dev, ndev, flags), "lhpc_spmv_plan_create")
         else:
             sp = np.ascontiguousarray(splits if splits is not None else [], dtype=np.int64)
-            self.splits = None if splits is None else [0] + [int(v) for v in sp] + [self.n_rows]
+            self.splits = None if splits is None else [0] + [int(v) for v in sp] + [a_rows]
             _check(lib.lhpc_spmv_plan_create_opts(
-                C.byref(self._h), self.dtype, self.n_rows, self.n_cols, self.nnz,
+                C.byref(self._h), self.dtype, a_rows, a_cols, self.nnz,
                 rp_ptr, rp_bits, col_ptr, val_ptr, dev, ndev,
                 flags, int(sp.shape[0]), sp.ctypes.data if sp.shape[0] else None, _opts(self._opts)),
                 "lhpc_spmv_plan_create_opts")
@@ -552,7 +563,9 @@ class SpMVPlan:
         synchronised; a CUDA tensor on the plan's device is taken in place,
         asynchronously on ``stream`` (default: torch's current stream) and
         without allocation (a SELL plan's first update excepted).  The plan
-        then equals a fresh plan built from the new values.  XSLICE,
+        then equals a fresh plan built from the new values.  A transposed
+        plan takes the values in the CSR order of A, the matrix it was given
+        (its first update allocates the buffer they are re-ordered into).  XSLICE,
         column-block and multi-device plans raise LhpcError
         (LHPC_ERR_UNSUPPORTED) and stay as they were: rebuild those."""
         return _set_values(self, lib.lhpc_spmv_plan_set_values, "lhpc_spmv_plan_set_values", val, stream)
@@ -623,17 +636,24 @@ class SpMMPlan:
     plan's device (LHPC_PLAN_DEVICE_INPUT).  A is copied to HBM once, as CSR.
     """
 
-    def __init__(self, row_ptr, col_idx, val, n_cols: int, flags: int = 0, device: Optional[int] = None):
+    def __init__(self, row_ptr, col_idx, val, n_cols: int, flags: int = 0, device: Optional[int] = None,
+                 transpose: bool = False):
+        """``transpose`` (LHPC_PLAN_TRANSPOSE): the plan is Aᵀ's, as for SpMVPlan."""
         a = _csr_arrays(row_ptr, col_idx, val)
+        if transpose:
+            flags |= PLAN_TRANSPOSE
         if a.device is not None:
             flags |= PLAN_DEVICE_INPUT
             if device is None:
                 device = a.device
         self.dtype, self.np_dtype = a.dtype, a.np_dtype
-        self.n_rows, self.n_cols, self.nnz = a.n_rows, int(n_cols), a.nnz
+        a_rows, a_cols = a.n_rows, int(n_cols)  # A's shape; the plan's attributes are the operator's
+        self.transposed = bool(flags & PLAN_TRANSPOSE)
+        self.n_rows, self.n_cols = (a_cols, a_rows) if self.transposed else (a_rows, a_cols)
+        self.nnz = a.nnz
         self._h = _p()
         _check(lib.lhpc_spmm_plan_create(
-            C.byref(self._h), self.dtype, self.n_rows, self.n_cols, self.nnz, a.rp_ptr, a.rp_bits, a.col_ptr,
+            C.byref(self._h), self.dtype, a_rows, a_cols, self.nnz, a.rp_ptr, a.rp_bits, a.col_ptr,
             a.val_ptr, -1 if device is None else int(device), flags), "lhpc_spmm_plan_create")
 
     def info(self) -> dict:
@@ -972,6 +992,72 @@ def coo_to_csr(n_rows: int, n_cols: int, rows, cols, vals, row_ptr_bits: int = 6
     _check(lib.lhpc_coo_to_csr(dtype, n_rows, n_cols, nnz, rp_, cp_, vp_, row_ptr.ctypes.data, row_ptr_bits,
                                col.ctypes.data, val.ctypes.data, C.byref(out_n), 0, None), "lhpc_coo_to_csr")
     return row_ptr, col[:out_n.value].copy(), val[:out_n.value].copy()
+
+
+def csr_transpose(row_ptr, col_idx, val, n_cols: int, return_perm: bool = False, stream=None):
+    """The CSR of Aᵀ on the GPU (lhpc_csr_transpose): ``(t_row_ptr, t_col_idx,
+    t_val)``, and ``perm`` (uint32 on the host, int32 tensor on the device)
+    with ``return_perm``: output entry q is input entry perm[q], the order of a
+    stable sort of the positions by column.  ``row_ptr`` int32/int64 (the
+    output keeps the width), ``col_idx`` int32, ``val`` float32/float64 or
+    None (pattern only: ``t_val`` is None): host numpy arrays → numpy arrays;
+    CUDA tensors → tensors on the same device, the work on ``stream``
+    (default: torch's current stream).  Duplicates are kept, rows of Aᵀ come
+    out with ascending columns.  The call returns synchronised."""
+    n_cols = int(n_cols)
+    if n_cols < 0:
+        raise ValueError("csr_transpose: n_cols must not be negative")
+    arrays = [row_ptr, col_idx] + ([] if val is None else [val])
+    on_dev = [_is_torch(a) and bool(a.is_cuda) for a in arrays]
+    if any(on_dev) != all(on_dev):
+        raise ValueError("csr_transpose: the arrays must all be host arrays or all be device tensors")
+    if on_dev[0]:
+        import torch
+        if row_ptr.dtype not in (torch.int32, torch.int64) or col_idx.dtype != torch.int32:
+            raise TypeError("csr_transpose: row_ptr must be int32 or int64 and col_idx int32")
+        if val is not None and val.dtype not in (torch.float32, torch.float64):
+            raise TypeError("csr_transpose: val must be float32 or float64")
+        if any(a.device != row_ptr.device for a in arrays):
+            raise ValueError("csr_transpose: the tensors must be on one device")
+        bits, f32 = 64 if row_ptr.dtype == torch.int64 else 32, val is None or val.dtype == torch.float32
+    else:
+        for a in arrays:
+            if not isinstance(a, np.ndarray):
+                raise TypeError(f"csr_transpose: expected numpy arrays or CUDA tensors, got {type(a)}")
+        if row_ptr.dtype not in (np.int32, np.int64) or col_idx.dtype != np.int32:
+            raise TypeError("csr_transpose: row_ptr must be int32 or int64 and col_idx int32")
+        if val is not None and val.dtype not in (np.float32, np.float64):
+            raise TypeError("csr_transpose: val must be float32 or float64")
+        bits, f32 = 64 if row_ptr.dtype == np.int64 else 32, val is None or val.dtype == np.float32
+    if any(a.ndim != 1 for a in arrays) or _numel(row_ptr) < 1:
+        raise ValueError("csr_transpose: row_ptr (n_rows + 1), col_idx and val (nnz) must be one-dimensional")
+    n_rows, nnz = _numel(row_ptr) - 1, _numel(col_idx)
+    if val is not None and _numel(val) != nnz:
+        raise ValueError(f"csr_transpose: expected {nnz} values, got {_numel(val)}")
+    ptrs = [_buf(a)[0] for a in arrays] + ([None] if val is None else [])
+    if nnz == 0:  # nothing to read: NULL for val and t_val alike
+        ptrs[2] = None
+    if on_dev[0]:
+        import torch
+        dev = row_ptr.device
+        t_rp = torch.empty(n_cols + 1, dtype=row_ptr.dtype, device=dev)
+        t_col = torch.empty(nnz, dtype=torch.int32, device=dev)
+        t_val = None if val is None else torch.empty(nnz, dtype=val.dtype, device=dev)
+        perm = torch.empty(nnz, dtype=torch.int32, device=dev) if return_perm else None
+        out = [t.data_ptr() if t is not None and t.numel() else None for t in (t_col, t_val, perm)]
+        with torch.cuda.device(dev):
+            _check(lib.lhpc_csr_transpose(F32 if f32 else F64, n_rows, n_cols, nnz, ptrs[0], bits, ptrs[1], ptrs[2],
+                                          t_rp.data_ptr(), out[0], out[1], out[2], 1,
+                                          _stream_ptr(_dev_stream(row_ptr, stream))), "lhpc_csr_transpose")
+    else:
+        t_rp = np.empty(n_cols + 1, dtype=row_ptr.dtype)
+        t_col = np.empty(nnz, dtype=np.int32)
+        t_val = None if val is None else np.empty(nnz, dtype=val.dtype)
+        perm = np.empty(nnz, dtype=np.uint32) if return_perm else None
+        _check(lib.lhpc_csr_transpose(F32 if f32 else F64, n_rows, n_cols, nnz, ptrs[0], bits, ptrs[1], ptrs[2],
+                                      t_rp.ctypes.data, t_col.ctypes.data, None if ptrs[2] is None else t_val.ctypes.data,
+                                      None if perm is None else perm.ctypes.data, 0, None), "lhpc_csr_transpose")
+    return (t_rp, t_col, t_val, perm) if return_perm else (t_rp, t_col, t_val)
 
 
 # ------------------------------------------------------------ files (.lcsr, Matrix Market)

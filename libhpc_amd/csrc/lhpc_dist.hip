@@ -957,6 +957,7 @@ extern "C" int lhpc_dist_spmv_plan_create_opts(lhpc_dist_spmv_plan **out, lhpc_d
         (dtype != LHPC_F32 && dtype != LHPC_F64) || (row_ptr_bits != 32 && row_ptr_bits != 64))
       return LHPC_ERR_INVALID_ARG;
     *out = nullptr;
+    if (flags & LHPC_PLAN_TRANSPOSE) return LHPC_ERR_UNSUPPORTED;  // the row-block split is that of A·x
     const int nr = comm->nranks, rk = comm->rank;
     const int64_t nb = static_cast<int64_t>(nr) * K;
     if (cuts[0] != 0 || cuts[nb] != n_rows) return LHPC_ERR_INVALID_ARG;

@@ -31,6 +31,7 @@
 #include <type_traits>
 
 #include "lhpc_common.hpp"
+#include "lhpc_sort.hpp"
 
 namespace lhpc {
 namespace {
@@ -401,32 +402,8 @@ __global__ __launch_bounds__(BT) LHPC_SORT_DS_ATTR void k_radix_downsweep(
   }
 }
 
-struct DevBuf {
-  void *p = nullptr;
-  hipStream_t s = nullptr;
-  ~DevBuf() {
-    if (p) (void)hipFreeAsync(p, s);
-  }
-  hipError_t alloc(size_t bytes, hipStream_t st) {
-    s = st;
-    return scratch_alloc(&p, bytes, st);  // library pool (lhpc_common.hpp)
-  }
-};
-
-// Staging buffers of the host-buffer entry points: plain hipMalloc (not the
-// stream-ordered pool) and synchronous copies.  Asynchronous pageable copies
-// into pool memory on the null stream were seen to land after the kernel
-// that read them (rows read as 0 in 4 of 25 runs of tests/cpp
-// test_sparse_grid gpu, the 4-entry Matrix Market case).  Every step of that
-// path was ordered on the one caller stream; DESIGN.md §9 traces it and
-// records what was ruled out.
-struct HostStage {
-  void *p = nullptr;
-  ~HostStage() {
-    if (p) (void)hipFree(p);
-  }
-  hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
-};
+// (DevBuf, the stream-ordered scratch owner, and HostStage, the staging
+// buffer of the host-buffer entry points: lhpc_sort.hpp)
 
 // resident downsweep blocks on the current device (CUs × blocks per CU),
 // cached per kernel and device (relaxed atomics: racing threads compute the
@@ -666,12 +643,6 @@ __global__ __launch_bounds__(kSortThreads) void k_coo_finish(const uint64_t *__r
   }
 }
 
-int bits_for(int64_t v) {  // bits to hold values in [0, v)
-  int b = 0;
-  while (b < 62 && (int64_t{1} << b) < v) ++b;
-  return b;
-}
-
 template <typename T>
 int coo_to_csr_dev(int64_t n_rows, int64_t n_cols, int64_t nnz, const int32_t *rows, const int32_t *cols,
                    const T *vals, void *row_ptr, int row_ptr_bits, int32_t *col_out, T *val_out,
@@ -734,6 +705,23 @@ int coo_to_csr_dev(int64_t n_rows, int64_t n_cols, int64_t nnz, const int32_t *r
 }
 
 }  // namespace
+
+int bits_for(int64_t v) {  // bits to hold values in [0, v)
+  int b = 0;
+  while (b < 62 && (int64_t{1} << b) < v) ++b;
+  return b;
+}
+
+// the variant lhpc_radix_sort_pairs_u32 runs (below), for lhpc_transpose.hip
+int sort_pairs_u32_dev(uint32_t *keys, uint32_t *vals, int64_t n, int begin_bit, int end_bit, hipStream_t s) {
+#ifdef LHPC_SORT_P32_VARIANT  // A/B builds
+  return radix_sort_dev<uint32_t, true, LHPC_SORT_P32_VARIANT>(keys, vals, n, begin_bit, end_bit, s);
+#else
+  static_assert(kSortPairsTile == 16 * 1024, "lhpc_sort.hpp names this variant's sub-tile");
+  return radix_sort_dev<uint32_t, true, 16, false, 1024>(keys, vals, n, begin_bit, end_bit, s);
+#endif
+}
+
 }  // namespace lhpc
 
 using namespace lhpc;

@@ -491,11 +491,15 @@ extern "C" int lhpc_spmm_plan_create(lhpc_spmm_plan **out, int dtype, int64_t n_
         (row_ptr_bits == 32 && nnz > INT32_MAX) || device < -1)
       return LHPC_ERR_INVALID_ARG;
     // there is one kernel family and no partial sums to choose
-    if (flags & ~static_cast<unsigned>(LHPC_PLAN_VALIDATE | LHPC_PLAN_DEVICE_INPUT)) return LHPC_ERR_INVALID_ARG;
+    if (flags & ~static_cast<unsigned>(LHPC_PLAN_VALIDATE | LHPC_PLAN_DEVICE_INPUT | LHPC_PLAN_TRANSPOSE))
+      return LHPC_ERR_INVALID_ARG;
+    const bool transpose = (flags & LHPC_PLAN_TRANSPOSE) != 0;
+    if (transpose && n_rows > INT32_MAX) return LHPC_ERR_INVALID_ARG;  // A's rows are the operator's columns
     RocTxRange rx("lhpc_spmm_plan_create");
     const bool device_input = (flags & LHPC_PLAN_DEVICE_INPUT) != 0;
     // always (LHPC_PLAN_VALIDATE is implied): the kernel indexes X by col_idx
-    if (!device_input) LHPC_TRY(validate_csr(row_ptr, row_ptr_bits, col_idx, n_rows, n_cols, nnz));
+    // (a transposed plan's A is checked on the device, lhpc_transpose.hip)
+    if (!device_input && !transpose) LHPC_TRY(validate_csr(row_ptr, row_ptr_bits, col_idx, n_rows, n_cols, nnz));
     int dev = device;
     if (dev < 0 ? hipGetDevice(&dev) != hipSuccess : hipSetDevice(dev) != hipSuccess) {
       (void)hipGetLastError();
@@ -507,10 +511,23 @@ extern "C" int lhpc_spmm_plan_create(lhpc_spmm_plan **out, int dtype, int64_t n_
     p->dtype = dtype;
     p->device = dev;
     p->rp64 = row_ptr_bits == 64;
-    p->n_rows = n_rows;
-    p->n_cols = n_cols;
+    p->n_rows = transpose ? n_cols : n_rows;
+    p->n_cols = transpose ? n_rows : n_cols;
     p->nnz = nnz;
-    const int st = plan_build(p, row_ptr, row_ptr_bits, col_idx, val, device_input);
+    int st;
+    if (transpose) {
+      // Aᵀ's arrays from the device transposition, then the device-input
+      // build; the plan keeps the permutation for set_values
+      TransposedCsr t;
+      st = dmalloc(reinterpret_cast<void **>(&p->d_tperm), static_cast<size_t>(nnz) * 4, p->bytes);
+      if (st == LHPC_OK)
+        st = transpose_for_plan(t, dtype == LHPC_F32 ? 4 : 8, n_rows, n_cols, nnz, row_ptr, row_ptr_bits, col_idx, val,
+                                device_input, p->d_tperm);
+      if (st == LHPC_OK)
+        st = plan_build(p, t.t_rp, row_ptr_bits, static_cast<const int32_t *>(t.t_col), t.t_val, true);
+    } else {
+      st = plan_build(p, row_ptr, row_ptr_bits, col_idx, val, device_input);
+    }
     if (st != LHPC_OK) {
       lhpc_spmm_plan_destroy(p);
       return st;
@@ -568,6 +585,29 @@ extern "C" int lhpc_spmm_plan_set_values(lhpc_spmm_plan *p, const void *val, int
     hipStream_t s = static_cast<hipStream_t>(stream);
     LHPC_HIP_TRY(hipSetDevice(p->device));
     const size_t bytes = static_cast<size_t>(nnz) * (p->dtype == LHPC_F32 ? 4 : 8);
+    if (p->d_tperm) {
+      // LHPC_PLAN_TRANSPOSE: val is in A's CSR order; through the plan's
+      // permutation into the staging buffer (allocated by the first update),
+      // then the one copy of every SpMM plan
+      if (!p->d_tval) {
+        LHPC_TRY(dmalloc(&p->d_tval, bytes, p->bytes));
+        LHPC_HIP_TRY(hipStreamSynchronize(s));
+      }
+      const size_t tsz = p->dtype == LHPC_F32 ? 4 : 8;
+      if (values_on_device) {
+        LHPC_TRY(gather_values(p->d_tval, val, p->d_tperm, nnz, tsz, s));
+        LHPC_HIP_TRY(hipMemcpyAsync(p->d_val, p->d_tval, bytes, hipMemcpyDeviceToDevice, s));
+        return LHPC_OK;
+      }
+      void *tmp = nullptr;  // stream-ordered library scratch, freed before return
+      LHPC_HIP_TRY(scratch_alloc(&tmp, bytes, s));
+      hipError_t e = hipMemcpyAsync(tmp, val, bytes, hipMemcpyHostToDevice, s);
+      int st = e == hipSuccess ? gather_values(p->d_tval, tmp, p->d_tperm, nnz, tsz, s) : static_cast<int>(e);
+      if (st == LHPC_OK) st = static_cast<int>(hipMemcpyAsync(p->d_val, p->d_tval, bytes, hipMemcpyDeviceToDevice, s));
+      (void)hipFreeAsync(tmp, s);
+      e = hipStreamSynchronize(s);
+      return st != LHPC_OK ? st : static_cast<int>(e);
+    }
     LHPC_HIP_TRY(hipMemcpyAsync(p->d_val, val, bytes,
                                 values_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
     if (!values_on_device) LHPC_HIP_TRY(hipStreamSynchronize(s));
@@ -596,7 +636,8 @@ extern "C" int lhpc_spmm_plan_destroy(lhpc_spmm_plan *p) {
     if (!p) return LHPC_OK;
     (void)hipSetDevice(p->device);
     for (void *q : {p->d_row_ptr, static_cast<void *>(p->d_col), p->d_val, static_cast<void *>(p->d_blocks),
-                    p->d_xstage, p->d_ystage, p->d_dpart, p->cg_vecs, p->cg_scal})
+                    p->d_xstage, p->d_ystage, p->d_dpart, p->cg_vecs, p->cg_scal, static_cast<void *>(p->d_tperm),
+                    p->d_tval})
       if (q) (void)hipFree(q);
     if (p->cg_host) (void)hipHostFree(p->cg_host);
     delete p;

@@ -36,6 +36,11 @@ struct lhpc_spmm_plan {
   size_t cg_vecs_bytes = 0, cg_scal_bytes = 0;
   void *cg_host = nullptr;
   size_t cg_host_bytes = 0;
+  // LHPC_PLAN_TRANSPOSE (the plan is Aᵀ's): entry q of Aᵀ is entry d_tperm[q]
+  // of the caller's A; lhpc_spmm_plan_set_values gathers the caller's values
+  // into d_tval (nnz values, allocated by the first update)
+  uint32_t *d_tperm = nullptr;
+  void *d_tval = nullptr;
 };
 
 namespace lhpc {

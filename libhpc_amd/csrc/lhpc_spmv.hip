@@ -464,11 +464,36 @@ int plan_create_impl(lhpc_spmv_plan **out, int dtype, int64_t n_rows, int64_t n_
   // plan, stream, comm stream (and RCCL comm) per device (lhpc_multi.hip)
   const bool multi = n_devices > 1 || (o.multi_force && n_devices == 1 && device_ids);
   const bool device_input = (flags & LHPC_PLAN_DEVICE_INPUT) != 0;
-  flags &= ~static_cast<unsigned>(LHPC_PLAN_DEVICE_INPUT);  // from here on src says where A lives
+  const bool transpose = (flags & LHPC_PLAN_TRANSPOSE) != 0;
+  flags &= ~static_cast<unsigned>(LHPC_PLAN_DEVICE_INPUT | LHPC_PLAN_TRANSPOSE);  // from here on src says where A lives
+  if (transpose) {
+    if (n_rows > INT32_MAX) return LHPC_ERR_INVALID_ARG;  // A's rows are the operator's columns
+    // row ranges and the row-block split are those of A·x
+    if (n_splits > 0 || multi) return LHPC_ERR_UNSUPPORTED;
+  }
 
   CsrSource src{RowPtrView{row_ptr, row_ptr_bits}, col_idx, val, nullptr};
   HostCopy host;
   int dev = 0;
+  if (transpose) {
+    // LHPC_PLAN_TRANSPOSE: A is transposed on the plan's device
+    // (lhpc_transpose.hip, which validates it there) and the plan is built
+    // from Aᵀ's arrays as from any device input; it keeps the permutation
+    LHPC_TRY(pick_device(device_ids, n_devices, dev));
+    PlanPtr p(new_plan(o, dtype, dev, n_cols, n_rows, nnz));
+    if (!p) return LHPC_ERR_ALLOC;
+    int64_t perm_bytes = 0;  // booked once the family stands (a refused XTILE build resets the count)
+    LHPC_TRY(dmalloc(reinterpret_cast<void **>(&p->d_tperm), static_cast<size_t>(nnz) * 4, perm_bytes));
+    TransposedCsr t;
+    LHPC_TRY(transpose_for_plan(t, dtype == LHPC_F32 ? 4 : 8, n_rows, n_cols, nnz, row_ptr, row_ptr_bits, col_idx, val,
+                                device_input, p->d_tperm));
+    src = CsrSource{RowPtrView{t.t_rp, row_ptr_bits}, static_cast<const int32_t *>(t.t_col), t.t_val, nullptr};
+    LHPC_TRY(device_source(src, host, n_cols, n_rows, nnz));
+    LHPC_TRY(build_single(p.get(), src, host, flags, 0));
+    p->bytes += perm_bytes;
+    *out = p.release();
+    return LHPC_OK;  // t: Aᵀ's arrays are freed now that the layout stands
+  }
   if (device_input) {
     LHPC_TRY(pick_device(device_ids, n_devices, dev));  // where the arrays are
     LHPC_TRY(device_source(src, host, n_rows, n_cols, nnz));
@@ -695,8 +720,30 @@ extern "C" int lhpc_spmv_plan_set_values(lhpc_spmv_plan *p, const void *val, int
     RocTxRange rx("lhpc_spmv_plan_set_values");
     hipStream_t s = static_cast<hipStream_t>(stream);
     LHPC_HIP_TRY(hipSetDevice(p->device));
-    if (values_on_device) return set_values_device(p, val, s);
     const size_t bytes = static_cast<size_t>(nnz) * (p->dtype == LHPC_F32 ? 4 : 8);
+    if (p->d_tperm) {
+      // LHPC_PLAN_TRANSPOSE: val is in A's CSR order; gathered through the
+      // plan's permutation into Aᵀ's order, then the family's update runs
+      // from that buffer.  The buffer comes with the first update.
+      if (!p->d_tval) {
+        LHPC_TRY(dmalloc(&p->d_tval, bytes, p->bytes));
+        LHPC_HIP_TRY(hipStreamSynchronize(s));
+      }
+      const size_t tsz = p->dtype == LHPC_F32 ? 4 : 8;
+      if (values_on_device) {
+        LHPC_TRY(gather_values(p->d_tval, val, p->d_tperm, nnz, tsz, s));
+        return set_values_device(p, p->d_tval, s);
+      }
+      void *tmp = nullptr;  // stream-ordered library scratch, freed before return
+      LHPC_HIP_TRY(scratch_alloc(&tmp, bytes, s));
+      hipError_t e = hipMemcpyAsync(tmp, val, bytes, hipMemcpyHostToDevice, s);
+      int st = e == hipSuccess ? gather_values(p->d_tval, tmp, p->d_tperm, nnz, tsz, s) : static_cast<int>(e);
+      if (st == LHPC_OK) st = set_values_device(p, p->d_tval, s);
+      (void)hipFreeAsync(tmp, s);
+      e = hipStreamSynchronize(s);
+      return st != LHPC_OK ? st : static_cast<int>(e);
+    }
+    if (values_on_device) return set_values_device(p, val, s);
     if (p->parts.empty() && p->kernel != LHPC_KERNEL_XTILE && p->kernel != LHPC_KERNEL_SELL) {
       // CSR order in the plan too: straight into place
       LHPC_HIP_TRY(hipMemcpyAsync(p->d_val, val, bytes, hipMemcpyHostToDevice, s));
@@ -769,7 +816,7 @@ extern "C" int lhpc_spmv_plan_destroy(lhpc_spmv_plan *p) {
                     static_cast<void *>(p->d_col16), static_cast<void *>(p->d_perm), p->d_xg,
                     static_cast<void *>(p->d_pieces_cp), static_cast<void *>(p->d_pext),
                     static_cast<void *>(p->d_carry), static_cast<void *>(p->d_sell_rp),
-                    static_cast<void *>(p->d_rec)})
+                    static_cast<void *>(p->d_rec), static_cast<void *>(p->d_tperm), p->d_tval})
       if (q) (void)hipFree(q);
     if (p->h_scalars) (void)hipHostFree(p->h_scalars);
     for (hipGraphExec_t g : p->cg_graph)

@@ -16,6 +16,7 @@
 
 #include <atomic>
 #include <cstdint>
+#include <initializer_list>
 #include <vector>
 
 #include "lhpc_common.hpp"
@@ -116,6 +117,12 @@ struct lhpc_spmv_plan {
   int xt_acc = 0;
   // single-process multi-device plan (n_devices > 1; lhpc_multi.hip)
   struct lhpc_multi *multi = nullptr;
+  // LHPC_PLAN_TRANSPOSE: the plan is Aᵀ's (n_rows, n_cols are the operator's).
+  // d_tperm: entry q of Aᵀ is entry d_tperm[q] of the caller's A (nnz words,
+  // lhpc_csr_transpose's perm); d_tval: lhpc_spmv_plan_set_values gathers the
+  // caller's values into it (nnz values, allocated by the first update)
+  uint32_t *d_tperm = nullptr;
+  void *d_tval = nullptr;
 };
 
 namespace lhpc {
@@ -208,6 +215,40 @@ bool is_gfx950(int dev);
 // decreases, row_ptr[n_rows] != nnz or a column is outside [0, n_cols)
 int validate_csr_device(const void *row_ptr, int row_ptr_bits, const int32_t *col_idx, int64_t n_rows,
                         int64_t n_cols, int64_t nnz);
+
+// ---- lhpc_transpose.hip (LHPC_PLAN_TRANSPOSE of both plan types)
+// lhpc_csr_transpose on device arrays of the current device (tsz: 4 or 8
+// bytes per value; val and t_val may both be null, perm may be null): A is
+// validated (LHPC_ERR_BAD_CSR), the work runs on s, s has drained on return
+int csr_transpose_dev(size_t tsz, int64_t n_rows, int64_t n_cols, int64_t nnz, const void *row_ptr, int bits,
+                      const int32_t *col_idx, const void *val, void *t_row_ptr, int32_t *t_col_idx, void *t_val,
+                      uint32_t *perm, hipStream_t s);
+// dst[q] = src[perm[q]] for q < n (device arrays, one launch on s)
+int gather_values(void *dst, const void *src, const uint32_t *perm, int64_t n, size_t tsz, hipStream_t s);
+// The arrays of Aᵀ for a plan build: A (host arrays, or device_input: arrays
+// on the current device) is uploaded if need be and transposed on the null
+// stream.  t_rp / t_col / t_val are temporaries the owner frees; perm
+// (plan-owned, nnz words) is written in place.
+struct TransposedCsr {
+  void *up_rp = nullptr, *up_col = nullptr, *up_val = nullptr;  // uploaded copies of host input
+  void *t_rp = nullptr, *t_col = nullptr, *t_val = nullptr;
+  TransposedCsr() = default;
+  TransposedCsr(const TransposedCsr &) = delete;
+  TransposedCsr &operator=(const TransposedCsr &) = delete;
+  void free_input() {
+    for (void **q : {&up_rp, &up_col, &up_val}) {
+      if (*q) (void)hipFree(*q);
+      *q = nullptr;
+    }
+  }
+  ~TransposedCsr() {
+    free_input();
+    for (void *q : {t_rp, t_col, t_val})
+      if (q) (void)hipFree(q);
+  }
+};
+int transpose_for_plan(TransposedCsr &t, size_t tsz, int64_t n_rows, int64_t n_cols, int64_t nnz, const void *row_ptr,
+                       int bits, const int32_t *col_idx, const void *val, bool device_input, uint32_t *perm);
 
 // ---- lhpc_spmv_csr.hip
 int csr_launch(const lhpc_spmv_plan *p, const void *x, void *y, hipStream_t s);
