@@ -362,7 +362,7 @@ int lhpc_spmv_plan_chunkrec(const lhpc_spmv_plan *plan, int *on, uint64_t *diges
  * Checked before anything is written (a refused call leaves the plan as it
  * was):
  *   LHPC_ERR_INVALID_ARG   null plan, null val with nnz > 0, nnz ≠ the plan's
- *   LHPC_ERR_BUSY          a lhpc_cg_solve is holding the plan
+ *   LHPC_ERR_BUSY          a lhpc_cg_solve or lhpc_bicgstab_solve is holding the plan
  *   LHPC_ERR_UNSUPPORTED   XSLICE plans and XTILE column-block plans (a
  *       value's position in their layout depends on col_idx, which the plan
  *       does not keep) and single-process multi-device plans (the layout
@@ -742,6 +742,69 @@ int lhpc_cg_solve(lhpc_spmv_plan *plan, const void *b, void *x, double tol,
                   double *resid_out, void *stream);
 int lhpc_vec_dot(int dtype, int64_t n, const void *a, const void *b,
                  double *out, void *stream);
+/*
+ * BiCGStab on an SpMV plan: A·x = b for a square A that need not be symmetric
+ * or positive definite (no reference counterpart).  It uses A·x only, so it
+ * accepts the plans lhpc_cg_solve accepts: every kernel family, row parts,
+ * LHPC_PLAN_TRANSPOSE (which then solves Aᵀ·x = b).
+ * b and x are HBM pointers of the plan's dtype; x holds the initial guess on
+ * entry and the result on return.  Synchronous.  LHPC_ERR_INVALID_ARG before
+ * the plan is read: null plan, null b or x, max_iter < 0, a tol that is not
+ * ≥ 0; then a plan that is not square.  check_every < 1 counts as 1.
+ * The recurrence, with element arithmetic in the plan's dtype, α, ω and β
+ * fp64 quotients cast to it, and every dot in fp64:
+ *   bb = b·b;  r = b − A·x;  r̂ = r;  p = r;  ρ = r̂·r;  rr = r·r
+ *   stop = tol²·(bb > 0 ? bb : 1);   rr ≤ stop: done at 0 iterations
+ *   for it = 1 … max_iter:
+ *     v = A·p;  σ = r̂·v;  α = ρ/σ
+ *     s = r − α·v;  ss = s·s
+ *     t = A·s;  ts = t·s;  tt = t·t;  ω = ts/tt    (ss ≤ stop: ω = 0, final step)
+ *     x += α·p + ω·s;  r = s − ω·t;  ρ' = r̂·r;  rr = r·r
+ *     rr ≤ stop (or final step): done at `it`
+ *     β = (ρ'/ρ)·(α/ω);  p = r + β·(p − ω·v);  ρ = ρ'
+ * The latch.  Convergence and breakdown are tested on the device, by
+ * one-block kernels, where σ, ω and ρ' / rr come into being; they keep a
+ * state word in HBM (active, done, broke down) and, beside it, the number of
+ * completed iterations and their rr, which stop changing when the state
+ * leaves "active".  Every vector kernel of the solver reads the state first
+ * and writes nothing once it is not active; the SpMVs of the remaining
+ * iterations of a block run on the frozen vectors and their results are
+ * ignored.  The host reads the latch after the set-up (iteration 0), then
+ * every check_every iterations and at max_iter: those are the only
+ * synchronisations.  So x, *iters_out and *resid_out are bit-identical for
+ * every check_every ≥ 1 and from run to run (the dots are summed in a fixed
+ * order that depends on n and the plan only); *iters_out (host, may be NULL)
+ * is the iteration at which rr ≤ stop first held — not a multiple of
+ * check_every — or max_iter, and *resid_out (host, may be NULL) is
+ * sqrt(max(rr, 0)) / sqrt(bb > 0 ? bb : 1) of the latched rr.  Running out of
+ * iterations is LHPC_OK, as in lhpc_cg_solve: compare *resid_out with tol.
+ * Breakdown (LHPC_ERR_INTERNAL; it happens on valid input, e.g. a
+ * skew-symmetric A, where r̂·v = 0):
+ *   σ, α, tt or ω not finite, or σ or ω zero while ss > stop — found before x
+ *   is written for that iteration — and ρ' zero at the end of an iteration
+ *   that has not converged: x is the iterate of the last completed iteration,
+ *   *iters_out its number (0: x is the initial guess, bit for bit) and
+ *   *resid_out its finite residual;
+ *   rr not finite (overflow): that iteration's x has been written and is
+ *   returned, *iters_out counts it and *resid_out is not finite.  A residual
+ *   of the initial guess that is not finite is reported at 0 iterations.
+ * Storage.  The work — the vectors r, r̂, p, v, s, t and a working x (the
+ * caller's x is copied in and out), device scalars, dot partials, a pinned
+ * host latch — belongs to the plan: allocated on the plan's device by the
+ * first solve (not counted in device_bytes, like lhpc_cg_solve's) and freed
+ * by lhpc_spmv_plan_destroy.  No allocation happens inside an iteration.  On
+ * a non-null stream with check_every ≥ 4 and an ADAPTIVE or SELL plan (one
+ * device, no parts) the check_every iterations between two reads of the latch
+ * are captured once as a linear HIP graph, kept with the plan and replayed
+ * (a refused capture falls back to the loop; graph and loop issue the same
+ * kernels in the same order, so their results are bit-identical).  The plan
+ * serves one solve at a time, of either kind: while a lhpc_bicgstab_solve or
+ * a lhpc_cg_solve holds it, a second one and lhpc_spmv_plan_set_values
+ * return LHPC_ERR_BUSY.
+ */
+int lhpc_bicgstab_solve(lhpc_spmv_plan *plan, const void *b, void *x, double tol,
+                        int max_iter, int check_every, int *iters_out,
+                        double *resid_out, void *stream);
 /*
  * Conjugate gradient for k right-hand sides on an SpMM plan: k independent CG
  * recurrences kept in step, so that one lhpc_spmm_dot per iteration serves

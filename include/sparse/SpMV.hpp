@@ -2,6 +2,7 @@
 //
 //   sparse::SpMVPlan<T>  RAII owner of the HBM copy of A (one per GPU)
 //   sparse::spmv(plan, x, y)  with x, y hpc::HPCHighDimensionFlatArray<1,T,...>
+//   sparse::bicgstab(plan, d_b, d_x, …)  solves A·x = b, A not symmetric
 //   sparse::default_options()  lhpc_options for pinning a kernel variant
 //                             (host, synchronous) or raw HBM pointers (async)
 // Forwards to the C ABI (include/lhpc.h); non-zero status → std::system_error
@@ -165,6 +166,20 @@ void spmv(SpMVPlan<T> &plan, const hpc::HPCHighDimensionFlatArray<1, T, LX, HX, 
 template <typename T>
 void spmv(SpMVPlan<T> &plan, const T *d_x, T *d_y, void *stream = nullptr) {
   lhpc::checkLhpc(lhpc_spmv(plan.native(), d_x, d_y, 1, stream));
+}
+
+// BiCGStab on the plan: A·x = b for a square A that need not be symmetric
+// (lhpc_bicgstab_solve).  d_b, d_x are HBM pointers; d_x holds the initial
+// guess on entry and the result on return.  Synchronous.  Returns {iterations,
+// ‖r‖/‖b‖}; a breakdown throws (LHPC_ERR_INTERNAL) with the iterate of the
+// last completed iteration in d_x.
+template <typename T>
+std::pair<int, double> bicgstab(SpMVPlan<T> &plan, const T *d_b, T *d_x, double tol = 1e-8, int max_iter = 1000,
+                                int check_every = 1, void *stream = nullptr) {
+  int iters = 0;
+  double resid = 0.0;
+  lhpc::checkLhpc(lhpc_bicgstab_solve(plan.native(), d_b, d_x, tol, max_iter, check_every, &iters, &resid, stream));
+  return {iters, resid};
 }
 
 // Multi-device plan, full replicas: d_x[d] / d_y[d] on device d; afterwards

@@ -25,7 +25,7 @@ from typing import Optional
 import numpy as np
 
 __all__ = [
-    "LhpcError", "lib", "F32", "F64", "device_count", "SpMVPlan", "SpMMPlan", "spmm_dot", "cg_multi",
+    "LhpcError", "lib", "F32", "F64", "device_count", "SpMVPlan", "SpMMPlan", "spmm_dot", "cg_multi", "bicgstab",
     "csr_partition_rows", "blur_x", "blur_y", "stencil7", "stencil7_planes",
     "gen_uniform_csr", "gen_powerlaw_csr", "gen_values", "padded_shape",
     "PLAN_VALIDATE", "PLAN_FORCE_ROWGROUP", "PLAN_FORCE_ADAPTIVE", "PLAN_FORCE_XSLICE", "PLAN_FAST_PARTIALS", "PLAN_EXACT_PARTIALS",
@@ -78,6 +78,7 @@ ABI_SYMBOLS = (
     "lhpc_spmv_plan_set_values", "lhpc_spmm_plan_set_values",
     "lhpc_spmv_plan_chunkrec",
     "lhpc_csr_transpose",
+    "lhpc_bicgstab_solve",
 )
 
 if not os.path.exists(LIB_PATH):
@@ -244,6 +245,7 @@ _sig("lhpc_scratch_poison", _i, _i64, _i, _p)
 _sig("lhpc_coo_to_csr", _i, _i, _i64, _i64, _i64, _p, _p, _p, _p, _i, _p, _p, C.POINTER(_i64), _i, _p)
 _sig("lhpc_csr_transpose", _i, _i, _i64, _i64, _i64, _p, _i, _p, _p, _p, _p, _p, _p, _i, _p)
 _sig("lhpc_cg_solve", _i, _p, _p, _p, _d, _i, _i, C.POINTER(_i), C.POINTER(_d), _p)
+_sig("lhpc_bicgstab_solve", _i, _p, _p, _p, _d, _i, _i, C.POINTER(_i), C.POINTER(_d), _p)
 _sig("lhpc_vec_dot", _i, _i, _i64, _p, _p, _p, _p)
 _sig("lhpc_spmv_dot", _i, _p, _p, _p, _p, _p, _p)
 _sig("lhpc_cg_step_xr", _i, _i, _i64, _p, _p, _p, _p, _p, _p, _p, _p)
@@ -1135,6 +1137,29 @@ def cg(plan: "SpMVPlan", b, x=None, tol: float = 1e-8, max_iter: int = 1000, che
     it, res = C.c_int(0), C.c_double(0.0)
     _check(lib.lhpc_cg_solve(plan._h, bp, xp, tol, max_iter, check_every, C.byref(it), C.byref(res),
                              _stream_ptr(st)), "lhpc_cg_solve")
+    return x, it.value, res.value
+
+
+def bicgstab(plan: "SpMVPlan", b, x=None, tol: float = 1e-8, max_iter: int = 1000, check_every: int = 1,
+             stream=None):
+    """Solve A·x = b (A square, the plan's matrix; it need not be symmetric)
+    by BiCGStab on the GPU.  ``b`` (and ``x``, the initial guess, default 0)
+    are device tensors of the plan's dtype; x is updated in place.  Returns
+    (x, iterations, ‖r‖/‖b‖); the result does not depend on ``check_every``.
+    A breakdown raises LhpcError (status LHPC_ERR_INTERNAL) and leaves the
+    iterate of the last completed iteration in a caller-supplied ``x``.  See
+    include/lhpc.h lhpc_bicgstab_solve."""
+    import torch
+    if x is None:
+        x = torch.zeros_like(b)
+    bp, bd = _buf(b)
+    xp, xd = _buf(x, writable=True)
+    if not (bd and xd):
+        raise ValueError("bicgstab: b and x must be device tensors")
+    st = _dev_stream(b, stream)
+    it, res = C.c_int(0), C.c_double(0.0)
+    _check(lib.lhpc_bicgstab_solve(plan._h, bp, xp, tol, max_iter, check_every, C.byref(it), C.byref(res),
+                                   _stream_ptr(st)), "lhpc_bicgstab_solve")
     return x, it.value, res.value
 
 

@@ -823,6 +823,10 @@ extern "C" int lhpc_spmv_plan_destroy(lhpc_spmv_plan *p) {
       if (g) (void)hipGraphExecDestroy(g);
     if (p->cg_vecs) (void)hipFree(p->cg_vecs);
     if (p->cg_scal) (void)hipFree(p->cg_scal);
+    if (p->bi_graph) (void)hipGraphExecDestroy(p->bi_graph);
+    if (p->bi_host) (void)hipHostFree(p->bi_host);
+    if (p->bi_vecs) (void)hipFree(p->bi_vecs);
+    if (p->bi_scal) (void)hipFree(p->bi_scal);
     delete p;
     return LHPC_OK;
   } LHPC_ABI_CATCH

@@ -47,6 +47,14 @@ struct lhpc_spmv_plan {
   hipGraphExec_t cg_graph[2] = {nullptr, nullptr};
   int cg_graph_iters[2] = {0, 0};
   std::atomic<int> cg_busy{0};  // a solve holds the work above (LHPC_ERR_BUSY for a second one)
+  // lhpc_bicgstab_solve's work (first solve; freed with the plan; under
+  // cg_busy too): r r̂ p v s t and a working x, device scalars + dot partials,
+  // the pinned latch the host reads, and the captured block of bi_graph_iters
+  // iterations
+  void *bi_vecs = nullptr;
+  double *bi_scal = nullptr, *bi_host = nullptr;
+  hipGraphExec_t bi_graph = nullptr;
+  int bi_graph_iters = 0;
   double *d_dpart = nullptr;  // lhpc_spmv_dot: per-block partials (ADAPTIVE / SELL), allocated on first use
   int kernel = LHPC_KERNEL_ROWGROUP;
   int L = 16, R = 4;
