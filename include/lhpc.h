@@ -706,6 +706,117 @@ int lhpc_csr_transpose(int dtype, int64_t n_rows, int64_t n_cols, int64_t nnz,
                        const void *val, void *t_row_ptr, int32_t *t_col_idx, void *t_val,
                        uint32_t *perm, int on_device, void *stream);
 
+/* ------------------------------------------------- CSR triangular solve
+ * x = L⁻¹·b or x = U⁻¹·b for a sparse triangle, level-scheduled, on the GPU:
+ * the kernel under Gauss–Seidel and SSOR sweeps and ILU(0) / IC(0)
+ * applications.  The reference has no counterpart (it has no SpMV).
+ *
+ * Input: a square CSR matrix A (n × n) whose rows may hold entries of both
+ * triangles (a whole A for a Gauss–Seidel sweep needs no splitting):
+ *   LHPC_TRSV_LOWER      keeps the entries with col < row and the diagonal
+ *   LHPC_TRSV_UPPER      keeps the entries with col > row and the diagonal
+ *   LHPC_TRSV_UNIT_DIAG  diagonal entries are ignored too, the diagonal is 1
+ * Entries of the other triangle are ignored.  Rows need not be sorted;
+ * duplicate off-diagonal coordinates are kept as separate products.
+ *
+ * Arithmetic.  Row i's solution is
+ *   s   = 0.0 (double);  for each kept off-diagonal entry p of row i, in CSR order:
+ *             s += (double)val[p] * (double)x[col[p]]   (product rounded, then the add)
+ *   x_i = (T)(((double)b_i − s) / (double)d_i)          non-unit
+ *   x_i = (T)((double)b_i − s)                          unit diagonal
+ * so every x_i is defined bit for bit, the same for every chain_rows, every
+ * stream and every run.  A zero d_i and non-finite inputs propagate by IEEE
+ * rules with no status; the layout's padding is skipped, never multiplied, so
+ * a non-finite x_j reaches only the rows that depend on row j.  x may be
+ * exactly b (in place); any other overlap is undefined.
+ * The row sum is sequential for every row length (one lane per row): a row
+ * of many hundred entries is correct but slow.
+ *
+ * Levels.  LOWER: level(i) = 0 when row i keeps no off-diagonal entry, else
+ * 1 + max level(col) over its kept off-diagonal entries; UPPER the same,
+ * walking the rows from n − 1 down.  Rows of one level are independent.
+ *   lhpc_sptrsv_levels  host only, touches no device: validates A
+ *       (LHPC_ERR_BAD_CSR for a non-monotone row_ptr, row_ptr[n] ≠ nnz, a
+ *       column outside [0, n) and, without LHPC_TRSV_UNIT_DIAG, a row with no
+ *       diagonal entry or with more than one) and writes level[0..n) and
+ *       *n_levels.  n = 0: 0 levels, LHPC_OK.
+ *
+ * Plan.  lhpc_sptrsv_plan_create analyses A on the host (one O(nnz) pass;
+ * LHPC_PLAN_DEVICE_INPUT arrays, on the plan's device, come to the host for
+ * it), copies what it needs and keeps no caller pointer.  Rows are sorted by
+ * level (ascending row index inside a level) and each level is cut into
+ * slices of 64 rows stored column-major as the SELL SpMV stores them: entry
+ * e of lane l at off + e·64 + l, padded to the slice's longest row with
+ * col = −1 (info.padded_entries in all).  Schedule, fixed at creation and
+ * info.launches long:
+ *   grid step   a level with more than chain_rows rows: one launch for the
+ *               level, a wave per slice, a lane per row; the earlier levels'
+ *               x is visible through the kernel boundary
+ *   chain step  a maximal run of consecutive levels of ≤ chain_rows rows
+ *               each: ONE launch of ONE 1024-thread workgroup that walks the
+ *               levels with a workgroup barrier between them
+ * No flag, spin or cross-workgroup wait is used anywhere.
+ *   chain_rows  0: the automatic threshold (256, measured: DESIGN.md §4.6); < 0: never chain (one
+ *               launch per level); > 0: the threshold itself.  No environment
+ *               variable is read.
+ * Level scheduling pays on orderings with few levels (multi-colour
+ * orderings); a natural-order grid has O(√n) levels and is bound by their
+ * number (DESIGN.md §4.6 has the measurements).
+ * Argument errors, before any device is touched:
+ *   LHPC_ERR_INVALID_ARG   NULL out or row_ptr, NULL col_idx or val with
+ *       nnz > 0, bad dtype or row_ptr_bits, a negative size, n > INT32_MAX,
+ *       nnz > INT32_MAX with 32-bit offsets, unknown trsv bits, a flag other
+ *       than LHPC_PLAN_VALIDATE (implied), LHPC_PLAN_DEVICE_INPUT and
+ *       LHPC_PLAN_TRANSPOSE
+ *   LHPC_ERR_UNSUPPORTED   LHPC_PLAN_TRANSPOSE (for Lᵀ run lhpc_csr_transpose
+ *       and ask for LHPC_TRSV_UPPER) and nnz ≥ 2^32 (32-bit source positions)
+ * then LHPC_ERR_BAD_CSR as for lhpc_sptrsv_levels (host input: still before
+ * any device is touched) and LHPC_ERR_NO_DEVICE without a gfx950 device.
+ * Limits of this version: sequential rows, host analysis, no TRANSPOSE flag,
+ * nnz < 2^32, one right-hand side.
+ *
+ * lhpc_sptrsv.  buffers_on_device != 0: b and x are HBM pointers on the
+ * plan's device and the call is info.launches kernel launches on `stream`
+ * only — no allocation, synchronisation or host copy, so it can be captured
+ * into a graph.  Otherwise b and x are host pointers staged through
+ * plan-owned buffers (allocated by the first such call) and the stream is
+ * synchronised before return.  n = 0: LHPC_OK, nothing is launched.  One host
+ * thread per plan.  LHPC_ERR_INVALID_ARG: NULL plan, NULL b or x with n > 0.
+ *
+ * lhpc_sptrsv_plan_set_values: the contract of lhpc_spmv_plan_set_values.
+ * val holds A's nnz values in the CSR order the plan was made from, ignored
+ * entries in their places; afterwards the plan gives the bits of a fresh plan
+ * built from the new values.  Only values move: the plan keeps the source
+ * position of every layout entry and of every diagonal (4 B each, counted in
+ * device_bytes).  Device values: one gather launch on `stream`, capturable;
+ * host values: staged through library scratch, stream synchronised.
+ * LHPC_ERR_INVALID_ARG for a NULL plan, NULL val with nnz > 0 or an nnz that
+ * is not the plan's (the plan stays as it was).
+ */
+enum lhpc_trsv_flags { LHPC_TRSV_LOWER = 0, LHPC_TRSV_UPPER = 1u << 0, LHPC_TRSV_UNIT_DIAG = 1u << 1 };
+typedef struct lhpc_sptrsv_plan lhpc_sptrsv_plan;
+typedef struct lhpc_sptrsv_plan_info {
+  int dtype, device, upper, unit_diag;
+  int64_t n, nnz;              /* kept off-diagonal entries                           */
+  int64_t n_levels, max_level_rows;
+  int64_t n_slices, padded_entries;
+  int chain_rows;              /* the threshold in force                              */
+  int launches;                /* kernel launches per lhpc_sptrsv call                */
+  int64_t device_bytes;
+} lhpc_sptrsv_plan_info;
+
+int lhpc_sptrsv_levels(int64_t n, int64_t nnz, const void *row_ptr, int row_ptr_bits,
+                       const int32_t *col_idx, unsigned trsv, int32_t *level, int64_t *n_levels);
+int lhpc_sptrsv_plan_create(lhpc_sptrsv_plan **out, int dtype, int64_t n, int64_t nnz,
+                            const void *row_ptr, int row_ptr_bits, const int32_t *col_idx,
+                            const void *val, unsigned trsv, int chain_rows,
+                            int device /* -1: current */, unsigned flags);
+int lhpc_sptrsv(lhpc_sptrsv_plan *plan, const void *b, void *x, int buffers_on_device, void *stream);
+int lhpc_sptrsv_plan_set_values(lhpc_sptrsv_plan *plan, const void *val, int64_t nnz,
+                                int values_on_device, void *stream);
+int lhpc_sptrsv_plan_info_get(const lhpc_sptrsv_plan *plan, lhpc_sptrsv_plan_info *info);
+int lhpc_sptrsv_plan_destroy(lhpc_sptrsv_plan *plan);
+
 /* ------------------------------------------------------------------- CG
  * Conjugate gradient on an SpMV plan (no reference
  * counterpart).  lhpc_cg_solve: b and x are HBM pointers of the plan's dtype

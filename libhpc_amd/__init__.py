@@ -31,6 +31,7 @@ __all__ = [
     "PLAN_VALIDATE", "PLAN_FORCE_ROWGROUP", "PLAN_FORCE_ADAPTIVE", "PLAN_FORCE_XSLICE", "PLAN_FAST_PARTIALS", "PLAN_EXACT_PARTIALS",
     "PLAN_FORCE_XTILE", "PLAN_FORCE_SELL", "PLAN_TRANSPOSE", "csr_transpose", "KERNEL_XTILE", "KERNEL_SELL",
     "KERNEL_ROWGROUP", "KERNEL_ADAPTIVE", "KERNEL_XSLICE",
+    "SpTRSVPlan", "SpTRSVPlanInfo", "sptrsv_levels", "TRSV_LOWER", "TRSV_UPPER", "TRSV_UNIT_DIAG",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -49,6 +50,7 @@ PLAN_FORCE_XTILE = 1 << 9
 PLAN_FORCE_SELL = 1 << 10
 PLAN_TRANSPOSE = 1 << 11
 KERNEL_ROWGROUP, KERNEL_ADAPTIVE, KERNEL_XSLICE, KERNEL_XTILE, KERNEL_SELL = 0, 1, 2, 3, 4
+TRSV_LOWER, TRSV_UPPER, TRSV_UNIT_DIAG = 0, 1 << 0, 1 << 1
 
 # every symbol include/lhpc.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = (
@@ -79,6 +81,8 @@ ABI_SYMBOLS = (
     "lhpc_spmv_plan_chunkrec",
     "lhpc_csr_transpose",
     "lhpc_bicgstab_solve",
+    "lhpc_sptrsv_levels", "lhpc_sptrsv_plan_create", "lhpc_sptrsv", "lhpc_sptrsv_plan_set_values",
+    "lhpc_sptrsv_plan_info_get", "lhpc_sptrsv_plan_destroy",
 )
 
 if not os.path.exists(LIB_PATH):
@@ -188,6 +192,16 @@ class SpMMPlanInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class SpTRSVPlanInfo(C.Structure):
+    """include/lhpc.h lhpc_sptrsv_plan_info."""
+    _fields_ = [("dtype", _i), ("device", _i), ("upper", _i), ("unit_diag", _i), ("n", _i64), ("nnz", _i64),
+                ("n_levels", _i64), ("max_level_rows", _i64), ("n_slices", _i64), ("padded_entries", _i64),
+                ("chain_rows", _i), ("launches", _i), ("device_bytes", _i64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 def _sig(name, res, *args):
     fn = getattr(lib, name)
     fn.restype = res
@@ -223,6 +237,12 @@ _sig("lhpc_spmm_dot", _i, _p, _i, _p, _i64, _p, _i64, _p, _i64, _p, _p)
 _sig("lhpc_cg_solve_multi", _i, _p, _i, _p, _i64, _p, _i64, C.c_double, _i, _i, _p, _p, _p)
 _sig("lhpc_spmm_plan_info_get", _i, _p, C.POINTER(SpMMPlanInfo))
 _sig("lhpc_spmm_plan_destroy", _i, _p)
+_sig("lhpc_sptrsv_levels", _i, _i64, _i64, _p, _i, _p, _u, _p, C.POINTER(_i64))
+_sig("lhpc_sptrsv_plan_create", _i, C.POINTER(_p), _i, _i64, _i64, _p, _i, _p, _p, _u, _i, _i, _u)
+_sig("lhpc_sptrsv", _i, _p, _p, _p, _i, _p)
+_sig("lhpc_sptrsv_plan_set_values", _i, _p, _p, _i64, _i, _p)
+_sig("lhpc_sptrsv_plan_info_get", _i, _p, C.POINTER(SpTRSVPlanInfo))
+_sig("lhpc_sptrsv_plan_destroy", _i, _p)
 _sig("lhpc_csr_partition_rows", _i, _p, _i, _i64, _i, _p)
 for _n in ("lhpc_blur_x_f32", "lhpc_blur_y_f32"):
     _sig(_n, _i, _p, _p, _i64, _i64, _i64, _i, _i, _p)
@@ -781,6 +801,114 @@ def cg_multi(plan: "SpMMPlan", B, X=None, tol: float = 1e-8, max_iter: int = 100
         err.iters, err.resid = iters, resid
         raise err
     return X, iters, resid
+
+
+# ------------------------------------------------------------ SpTRSV
+def _trsv_bits(upper, unit_diag) -> int:
+    return (TRSV_UPPER if upper else TRSV_LOWER) | (TRSV_UNIT_DIAG if unit_diag else 0)
+
+
+def sptrsv_levels(row_ptr, col_idx, upper: bool = False, unit_diag: bool = False):
+    """``(level, n_levels)`` of the triangle of a square CSR matrix
+    (lhpc_sptrsv_levels; host arrays, no device is touched): level[i] = 0 for
+    a row without kept off-diagonal entries, else 1 + the highest level among
+    the rows it depends on.  An invalid matrix, or (without ``unit_diag``) a
+    row without exactly one diagonal entry, raises LhpcError (LHPC_ERR_BAD_CSR)."""
+    row_ptr = np.ascontiguousarray(row_ptr)
+    col_idx = np.ascontiguousarray(col_idx, dtype=np.int32)
+    if row_ptr.dtype not in (np.int32, np.int64):
+        raise TypeError("row_ptr must be int32 or int64")
+    n = int(row_ptr.shape[0] - 1)
+    level = np.empty(n, dtype=np.int32)
+    n_levels = _i64(0)
+    _check(lib.lhpc_sptrsv_levels(n, int(col_idx.shape[0]), row_ptr.ctypes.data, row_ptr.dtype.itemsize * 8,
+                                  col_idx.ctypes.data if col_idx.size else None, _trsv_bits(upper, unit_diag),
+                                  level.ctypes.data if n else None, C.byref(n_levels)), "lhpc_sptrsv_levels")
+    return level, int(n_levels.value)
+
+
+class SpTRSVPlan:
+    """RAII plan for x = L⁻¹·b or x = U⁻¹·b, level-scheduled (mirrors
+    sparse::SpTRSVPlan<T> in include/sparse/SpTRSV.hpp; C ABI lhpc_sptrsv_*).
+
+    ``row_ptr`` int32/int64 (n+1), ``col_idx`` int32 (nnz), ``val``
+    float32/float64 (nnz) of a square matrix: host numpy arrays, or CUDA torch
+    tensors on the plan's device (LHPC_PLAN_DEVICE_INPUT).  The rows may hold
+    both triangles: ``upper=False`` keeps col < row and the diagonal,
+    ``upper=True`` col > row and the diagonal; ``unit_diag`` ignores the
+    diagonal entries and takes 1.  ``chain_rows``: 0 automatic, < 0 never
+    chain, > 0 the largest level a chain step takes (include/lhpc.h)."""
+
+    def __init__(self, row_ptr, col_idx, val, upper: bool = False, unit_diag: bool = False, chain_rows: int = 0,
+                 flags: int = 0, device: Optional[int] = None):
+        a = _csr_arrays(row_ptr, col_idx, val)
+        if a.device is not None:
+            flags |= PLAN_DEVICE_INPUT
+            if device is None:
+                device = a.device
+        self.dtype, self.np_dtype = a.dtype, a.np_dtype
+        self.n, self.nnz = a.n_rows, a.nnz
+        self.upper, self.unit_diag = bool(upper), bool(unit_diag)
+        self._h = _p()
+        _check(lib.lhpc_sptrsv_plan_create(
+            C.byref(self._h), self.dtype, self.n, self.nnz, a.rp_ptr, a.rp_bits, a.col_ptr if self.nnz else None,
+            a.val_ptr if self.nnz else None, _trsv_bits(upper, unit_diag), int(chain_rows),
+            -1 if device is None else int(device), flags), "lhpc_sptrsv_plan_create")
+
+    def info(self) -> dict:
+        inf = SpTRSVPlanInfo()
+        _check(lib.lhpc_sptrsv_plan_info_get(self._h, C.byref(inf)), "lhpc_sptrsv_plan_info_get")
+        return inf.as_dict()
+
+    def __call__(self, b, x=None, stream=None):
+        """x = T⁻¹·b.  numpy in → numpy out (synchronous); torch CUDA tensors →
+        asynchronous on ``stream`` (default: torch's current stream).  ``x``
+        may be ``b`` itself (in place); allocated when None."""
+        if x is None:
+            if _is_torch(b):
+                import torch
+                x = torch.empty(self.n, dtype=b.dtype, device=b.device)
+            else:
+                x = np.empty(self.n, dtype=self.np_dtype)
+        if b.shape[0] < self.n or x.shape[0] < self.n:
+            raise ValueError("b/x too short for the plan")
+        for t in (b, x):
+            if _is_torch(t):
+                import torch
+                if t.dtype != (torch.float32 if self.dtype == F32 else torch.float64):
+                    raise TypeError(f"expected dtype {self.np_dtype}, got {t.dtype}")
+        bp, bd = _buf(b, None if _is_torch(b) else self.np_dtype)
+        xp, xd = _buf(x, None if _is_torch(x) else self.np_dtype, writable=True)
+        if bd != xd:
+            raise ValueError("b and x must both be host or both be device buffers")
+        if bd and stream is None:
+            import torch
+            stream = torch.cuda.current_stream(x.device)
+        _check(lib.lhpc_sptrsv(self._h, bp, xp, int(bd), _stream_ptr(stream)), "lhpc_sptrsv")
+        return x
+
+    def set_values(self, val, stream=None):
+        """Same structure, new values (lhpc_sptrsv_plan_set_values): ``val``
+        holds the matrix's nnz values in the CSR order the plan was built
+        from, ignored entries in their places; as ``SpMVPlan.set_values``."""
+        return _set_values(self, lib.lhpc_sptrsv_plan_set_values, "lhpc_sptrsv_plan_set_values", val, stream)
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            lib.lhpc_sptrsv_plan_destroy(self._h)
+            self._h = _p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
 
 def csr_partition_rows(row_ptr: np.ndarray, parts: int) -> np.ndarray:
